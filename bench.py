@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the openGPC hot path (preprocess + hash + match) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 is the ONE command at any N: with N > 1 and no WORLD_SIZE in the environment the script starts its own N rank processes
 (one per GPU, RCCL between them) before anything touches a GPU, relays rank 0's JSON line and exits with the ranks' status;
@@ -17,10 +17,16 @@ Pairs shard embarrassingly (pair i -> rank i mod N); the only coll
 the timing barrier / MAX and a gather of per-rank counters.  Prints ONE JSON line on rank 0.
 
 A timed WINDOW is exactly K steps bracketed by barrier + device sync on both sides (the driver's
-contract).  K = 20 steps last ~23 ms, too short to be seen from outside, so the window is repeated
-(--windows, default 260 => the timed windows keep the GPU busy for ~6 s) and the MEDIAN window is
-reported; min / max are in the line.  The reference's own timed region is host-to-host: `pcie_inclusive` measures that
-in the same run and `speedup_vs_cpu_1thread` compares like with like.
+contract): a plain run sets up, warms up (at least W steps and WARMUP_MIN_S seconds), times ONE window of K steps and
+prints the line, whose `value` and `ms_per_step` are that window's.  --windows M repeats the window and reports the
+MEDIAN (min / max in the line).
+--dump-outputs DIR writes what the last timed step computed as .npy files (dump_outputs below).
+
+--full adds everything else the line has carried: the per-kernel table and roofline, the parity gate against the
+oracle, the CPU baseline, the strong-scaling and 32-pair legs, the two-lane pipeline, the single-pair step and the
+host-to-host (`pcie_inclusive`) legs.  The reference's own timed region is host-to-host: `pcie_inclusive` measures that
+in the same run and `speedup_vs_cpu_1thread` compares like with like.  The side legs time windows of at most
+FULL_WINDOW_STEPS steps, so a --full run lasts about as long at any K.
 """
 import argparse
 import json
@@ -33,29 +39,42 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 achievable
+WARMUP_MIN_S = 0.3      # the warm-up runs at least --warmup steps AND this long on the GPU (clocks up: after 3 steps a
+                        # 20-step window still runs ~9 % slow, after 0.3 s it runs like the median of many windows)
+FULL_WINDOW_STEPS = 20  # steps per window of the --full side legs (at most; fewer when --steps is smaller)
+DUMP_PAIRS = 12         # pairs whose supports --dump-outputs writes (a fixed, seeded sample of the batch)
+DUMP_SEED = 20260
+DUMP_BYTES = 48 << 20   # cap on the sampled supports (float32 x, y, d): the files stay under 64 MB at any size
 
 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=260,
-                    help="timed windows of --steps steps each (every one bracketed by barrier + sync); the median is reported")
+    ap.add_argument("--warmup", type=int, default=3,
+                    help="untimed steps before the timed ones: at least this many, and at least WARMUP_MIN_S seconds of them")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="timed windows of --steps steps each (every one bracketed by barrier + sync); the median is reported. "
+                         "Default 1: exactly --steps timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements and checks: per-kernel table and roofline, parity gate against the "
+                         "oracle, CPU baseline, strong-scaling / 32-pair / two-lane / single-pair / host-to-host legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--batch", type=int, default=256,
                     help="pairs per GPU per step: BASELINE configs[3]'s batch of 256 pairs, one such batch per GPU")
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--height", type=int, default=436)
     ap.add_argument("--forest", default=os.path.join(ROOT, "forests", "defaultZeroForest.txt"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--verify-pairs", type=int, default=16, help="pairs per rank checked against the oracle (spread over the batch)")
+    ap.add_argument("--no-verify", action="store_true", help="(--full) skip the parity gate")
+    ap.add_argument("--verify-pairs", type=int, default=16, help="(--full) pairs per rank checked against the oracle (spread over the batch)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the single-pair, two-stream and PCIe-inclusive side measurements (profiling runs: every "
+                    help="(--full) skip the single-pair, two-stream and PCIe-inclusive side measurements (profiling runs: every "
                          "launch of a kernel then has the same grid, so rocprofv3's averages match the HIP-event ones)")
     ap.add_argument("--host-path", action="store_true",
-                    help="measure the host-to-host call on every rank even with --no-extras (rehearsals of the N > 1 line)")
+                    help="(--full) measure the host-to-host call on every rank even with --no-extras (rehearsals of the N > 1 line)")
     ap.add_argument("--pipeline", type=int, default=1,
                     help="contexts (HIP streams + workspaces) the steps alternate over; 1 = strictly serial steps")
     return ap.parse_args()
@@ -220,6 +239,29 @@ def bytes_text(fused):
             "k_gather_rows": "16 B per support"}
 
 
+def dump_outputs(out, cnts, ncs, B):
+    """What the caller of the batched device path receives, from the buffers of one step, as float arrays:
+    counts [B] and candidates [B][2] (left, right) of every pair; the supports (x, y, d) of a fixed, seeded sample of
+    DUMP_PAIRS pairs, concatenated in pair order (sample_pairs: which pairs; sample_offsets: where each one's rows start).
+    x, y and d are exact in float32 (d is the gpc_support's float); each pair's rows are capped so that the sample stays
+    within DUMP_BYTES."""
+    import numpy as np
+    counts = cnts.cpu().numpy().astype(np.int64)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(B, min(B, DUMP_PAIRS), replace=False))
+    cap_rows = DUMP_BYTES // (12 * len(pick))
+    parts, offs = [], [0]
+    for j in pick:
+        a = out[int(j), : min(int(counts[j]), cap_rows)].cpu().numpy()
+        sup = np.empty(a.shape, np.float32)
+        sup[:, :2] = a[:, :2]
+        sup[:, 2] = a[:, 2].view(np.float32)
+        parts.append(sup)
+        offs.append(offs[-1] + len(sup))
+    return {"counts": counts.astype(np.float64), "candidates": ncs.cpu().numpy().astype(np.float64),
+            "sample_pairs": pick.astype(np.float64), "sample_offsets": np.asarray(offs, np.float64),
+            "sample_supports": np.concatenate(parts)}
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -291,53 +333,72 @@ def main():
             c.synchronize()  # the streams the kernels run on
         torch.cuda.synchronize(dev)
 
-    for _ in range(max(args.warmup, P)):
+    n_warm = max(args.warmup, P)
+    t_warm = time.perf_counter()
+    for _ in range(n_warm):
         step()
     device_sync()
+    while time.perf_counter() - t_warm < WARMUP_MIN_S:
+        for _ in range(8):
+            step()
+        n_warm += 8
+        device_sync()
 
-    # ---- which kernel dominates?  a few serial steps with every kernel bracketed by HIP events on the stream
-    #      the kernels run on (not part of `value`); the slowest one is then the only kernel bracketed inside
-    #      the timed windows, so the other launches carry no event records
-    def bracket_all(nsteps):
-        ctx.enable_kernel_timing(True)
-        ctx.reset_kernel_timing()
-        for _ in range(nsteps):
-            ctx.match_batch_device(d_L.data_ptr(), d_R.data_ptr(), W, H, B, settings, d_out.data_ptr(), cap,
-                                   d_counts.data_ptr(), d_ncand.data_ptr())
-        kt = {k: v for k, v in ctx.kernel_times().items() if v[1]}
-        ctx.enable_kernel_timing(False)
-        return kt
-
-    ktimes = bracket_all(4)
-    launch_names = ctx.kernel_launch_names()
-    dom_slot = max(ktimes.items(), key=lambda kv: kv[1][0] / kv[1][1])[0]
-
-    for c in ctxs:
-        c.enable_kernel_timing(True, only=[dom_slot])
-        c.reset_kernel_timing()
+    # ---- the headline: --windows windows (default ONE) of exactly --steps steps, no event records inside
     step_no[0] = 0
     windows = [gdist.timed_steps(step, args.steps, device_sync) for _ in range(max(1, args.windows))]
-    dom_ms, dom_n = 0.0, 0
-    for c in ctxs:
-        ms, n = c.kernel_times()[dom_slot]
-        dom_ms += ms
-        dom_n += n
-        c.enable_kernel_timing(False)
+    last = (step_no[0] - 1) % P   # the output set the last timed step wrote
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dump_outputs(d_outs[last], d_cnts[last], d_ncs[last], B).items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+    counts = d_cnts[last].cpu().numpy().astype(np.int64)
+    ncand = d_ncs[last].cpu().numpy().astype(np.int64)
+    full = args.full
+    xs = max(1, min(args.steps, FULL_WINDOW_STEPS))   # steps per window of the --full side legs
 
-    # per-kernel table: serial steps with every kernel bracketed, run right behind the timed windows (the clocks are
-    # where the windows left them: the first launches after an idle second run several per cent slower)
-    bracket_all(5)            # (the first launches with every kernel bracketed run a few per cent slower: not counted)
-    ktimes = bracket_all(20)
+    ktimes, launch_names, dom_slot, dom_ms, dom_n = {}, {}, None, 0.0, 0
+    if full:
+        # ---- which kernel dominates?  a few serial steps with every kernel bracketed by HIP events on the stream
+        #      the kernels run on (not part of `value`); the slowest one is then the only kernel bracketed inside
+        #      40 windows of the same steps, so the other launches carry no event records
+        def bracket_all(nsteps):
+            ctx.enable_kernel_timing(True)
+            ctx.reset_kernel_timing()
+            for _ in range(nsteps):
+                ctx.match_batch_device(d_L.data_ptr(), d_R.data_ptr(), W, H, B, settings, d_out.data_ptr(), cap,
+                                       d_counts.data_ptr(), d_ncand.data_ptr())
+            kt = {k: v for k, v in ctx.kernel_times().items() if v[1]}
+            ctx.enable_kernel_timing(False)
+            return kt
 
-    counts = d_counts.cpu().numpy().astype(np.int64)
-    ncand = d_ncand.cpu().numpy().astype(np.int64)
+        ktimes = bracket_all(4)
+        launch_names = ctx.kernel_launch_names()
+        dom_slot = max(ktimes.items(), key=lambda kv: kv[1][0] / kv[1][1])[0]
+
+        for c in ctxs:
+            c.enable_kernel_timing(True, only=[dom_slot])
+            c.reset_kernel_timing()
+        step_no[0] = 0
+        for _ in range(40):
+            gdist.timed_steps(step, xs, device_sync)
+        for c in ctxs:
+            ms, n = c.kernel_times()[dom_slot]
+            dom_ms += ms
+            dom_n += n
+            c.enable_kernel_timing(False)
+
+        # per-kernel table: serial steps with every kernel bracketed, run right behind the timed windows (the clocks are
+        # where the windows left them: the first launches after an idle second run several per cent slower)
+        bracket_all(5)            # (the first launches with every kernel bracketed run a few per cent slower: not counted)
+        ktimes = bracket_all(20)
 
     # ---- BASELINE configs[3] AS WRITTEN: ONE batch of 256 pairs shared by the N GPUs, 256 / N pairs per rank and step
     #      (the headline above scales weakly: 256 pairs per rank at any N).  The same barrier-bracketed windows, fewer of
     #      them; at one rank also the 32-pair step that is a rank's share at N = 8.  Not part of `value`.
     strong_windows, share8_windows = [], []
     Bs = max(1, min(B, 256 // world))
-    if not args.no_extras or args.host_path:
+    if full and (not args.no_extras or args.host_path):
         def step_n(npairs):
             def f():
                 ctx.match_batch_device(d_L.data_ptr(), d_R.data_ptr(), W, H, npairs, settings, d_outs[-1].data_ptr(), cap,
@@ -346,12 +407,12 @@ def main():
         for _ in range(5):
             step_n(Bs)()
         device_sync()
-        strong_windows = [gdist.timed_steps(step_n(Bs), args.steps, device_sync) for _ in range(40)]
+        strong_windows = [gdist.timed_steps(step_n(Bs), xs, device_sync) for _ in range(40)]
         if world == 1 and B >= 32:
             for _ in range(5):
                 step_n(32)()
             device_sync()
-            share8_windows = [gdist.timed_steps(step_n(32), args.steps, device_sync) for _ in range(40)]
+            share8_windows = [gdist.timed_steps(step_n(32), xs, device_sync) for _ in range(40)]
         # (d_outs[-1] was overwritten by shorter batches: the arrays compared below are d_out's, written by the timed windows)
         if P == 1:
             ctx.match_batch_device(d_L.data_ptr(), d_R.data_ptr(), W, H, B, settings, d_out.data_ptr(), cap,
@@ -361,7 +422,7 @@ def main():
     # ---- parity gate on the bench's own data: pairs spread over this rank's batch against the oracle
     #      (checker only; the -O3 build of the C restatement, held equal to the plain build by tests/)
     n_verified, verified = 0, None
-    if not args.no_verify:
+    if full and not args.no_verify:
         from oracle.pyoracle import Oracle, sparsematch_settings
         o = Oracle(fast=True)
         rc, f = o.read_forest(args.forest, W, H)
@@ -392,7 +453,7 @@ def main():
     host_reps, host_times, host_ok, host_threads, child_rec = 15, [], True, 0, None
     packed_reps, packed_times = 9, []
     inproc_times = []
-    if not args.no_extras or args.host_path:
+    if full and (not args.no_extras or args.host_path):
         child = HostChild(B, W, H, args.forest, dev_index)
         try:
             child.wait_ready()                    # 5 untimed calls: page-locked buffers touched, workers and clocks warm
@@ -449,12 +510,12 @@ def main():
     strong = None
     if strong_windows:
         sw = np.sort(gdist.gather_stats(strong_windows, device=stat_dev).numpy().max(axis=0))   # per window: the slowest rank
-        ts = float(sw[len(sw) // 2]) / args.steps
+        ts = float(sw[len(sw) // 2]) / xs
         strong = {"pairs_per_rank_per_step": Bs, "pairs_per_step": Bs * world, "ms_per_step": round(ts * 1e3, 4),
                   "value": round(2.0 * W * H * Bs * world / ts / 1e6, 1), "unit": "Mpix/s",
-                  "ms_per_step_min": round(float(sw[0]) / args.steps * 1e3, 4), "ms_per_step_max": round(float(sw[-1]) / args.steps * 1e3, 4),
+                  "ms_per_step_min": round(float(sw[0]) / xs * 1e3, 4), "ms_per_step_max": round(float(sw[-1]) / xs * 1e3, 4),
                   "note": "BASELINE configs[3] as written: one batch of 256 pairs over the %d GPU(s), %d pairs per rank and step, "
-                          "device-resident like `value`; median of %d windows of %d steps" % (world, Bs, len(sw), args.steps)}
+                          "device-resident like `value`; median of %d windows of %d steps" % (world, Bs, len(sw), xs)}
     if float(allr[:, 3].min()) < 1.0:
         raise SystemExit("bench.py: GPU supports differ from the oracle on some rank -- refusing to report a number")
     nh, npk = len(host_times), len(packed_times)
@@ -490,66 +551,68 @@ def main():
         mpix_per_step = 2.0 * W * H * pairs_per_step / 1e6
         value = mpix_per_step * args.steps / t_med
 
-        # ---- roofline of the dominant kernel: HBM bytes it must move (its formats) / HIP-event time
-        N_step = float(ncand.sum())
-        M_step = float(counts.sum())
-        fused = "k_gather_rows" not in ktimes   # the join wrote the supports itself (k_rowjoin.h, FUSE)
-        alg = compulsory_bytes(W, H, B, M_step, fused)
-        BYTES_TEXT = bytes_text(fused)
-        kinfo = {}
-        for name, (ms, n) in ktimes.items():
-            kinfo[name] = {"kernel": launch_names.get(name, name), "avg_us": round(1e3 * ms / n, 2), "launches": n}
-            if name in alg:
-                kinfo[name]["hbm_GBs"] = round(alg[name] / (ms / n * 1e-3) / 1e9, 1)
-                kinfo[name]["hbm_frac"] = round(alg[name] / (ms / n * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-        dom_us = 1e3 * dom_ms / max(dom_n, 1)
-        achieved = alg.get(dom_slot, 0.0) / (dom_us * 1e-6) / 1e9 if dom_ms > 0 else 0.0
-        # counters of the same workload from the committed rocprofv3 --pmc passes (never measured here)
-        prof, valu_prof = None, None
-        ppath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(ppath):
-            try:
-                with open(ppath) as fh:
-                    tj = json.load(fh)
-                prof = tj.get("%s@%dx%dx%d" % (dom_slot, W, H, B))
-                # (the kernels are bound by vector-instruction issue, not by HBM: the committed PMC passes say how busy the VALUs were)
-                valu_prof = {k.split("@")[1]: v for k, v in tj.items() if k.startswith("valu_issue@") and k.endswith("@%dx%dx%d" % (W, H, B))} or None
-            except Exception:
-                prof = None
-        # SURVEY.md 8d's whole-pipeline figure: A = 10*W*H + 48*N + 12*M bytes per pair of a sort-based
-        # matcher whose sort streams through HBM (this build keeps it in LDS: comparable across builds,
-        # not a statement about traffic)
-        a_pair = (10.0 * W * H * B + 48.0 * N_step + 12.0 * M_step) / B
-        roofline = {
-            "bound": "hbm",
-            "kernel": launch_names.get(dom_slot, dom_slot),
-            "achieved": round(achieved, 1),
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 4),
-            "traffic": None,
-            "traffic_from_profiles": prof,
-            "valu_issue_from_profiles": valu_prof,
-            "alg_bytes_per_launch": alg.get(dom_slot),
-            "avg_launch_us": round(dom_us, 2),
-            "launches_timed": dom_n,
-            "pipeline_alg_bytes_per_pair": a_pair,
-            "pipeline_alg_GBs_equivalent": round(a_pair * pairs_per_step * args.steps / t_med / 1e9, 1),
-            "pipeline_compulsory_frac": round(sum(alg.values()) * world * args.steps / t_med / 1e9 / HBM_PEAK_GBS, 4),
-            "note": "achieved = bytes the dominant kernel must read + write per launch given its formats (DESIGN.md 4: "
-                    "%s) / mean HIP-event duration of its %d launches inside the timed windows, on the stream it runs on.  "
-                    "The kernel keeps the reference's sort in LDS and is bound by LDS / issue, not by HBM: `frac` says how "
-                    "far below the HBM roof that leaves it.  `traffic` is not measured by this script; "
-                    "`traffic_from_profiles` = 2*FETCH_SIZE + WRITE_SIZE of the committed rocprofv3 --pmc passes.  "
-                    "pipeline_alg_GBs_equivalent = SURVEY 8d's A*pairs/t: the rate a matcher whose sort streams through HBM "
-                    "would need for this throughput -- NOT traffic and not a fraction of anything (this build's sort never "
-                    "leaves LDS, so it can exceed the peak); pipeline_compulsory_frac = sum of the kernels' compulsory bytes / "
-                    "step time / peak." % (BYTES_TEXT.get(dom_slot, ""), dom_n),
-            "kernels": kinfo,
-        }
+        roofline = None
+        if full:
+            # ---- roofline of the dominant kernel: HBM bytes it must move (its formats) / HIP-event time
+            N_step = float(ncand.sum())
+            M_step = float(counts.sum())
+            fused = "k_gather_rows" not in ktimes   # the join wrote the supports itself (k_rowjoin.h, FUSE)
+            alg = compulsory_bytes(W, H, B, M_step, fused)
+            BYTES_TEXT = bytes_text(fused)
+            kinfo = {}
+            for name, (ms, n) in ktimes.items():
+                kinfo[name] = {"kernel": launch_names.get(name, name), "avg_us": round(1e3 * ms / n, 2), "launches": n}
+                if name in alg:
+                    kinfo[name]["hbm_GBs"] = round(alg[name] / (ms / n * 1e-3) / 1e9, 1)
+                    kinfo[name]["hbm_frac"] = round(alg[name] / (ms / n * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+            dom_us = 1e3 * dom_ms / max(dom_n, 1)
+            achieved = alg.get(dom_slot, 0.0) / (dom_us * 1e-6) / 1e9 if dom_ms > 0 else 0.0
+            # counters of the same workload from the committed rocprofv3 --pmc passes (never measured here)
+            prof, valu_prof = None, None
+            ppath = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(ppath):
+                try:
+                    with open(ppath) as fh:
+                        tj = json.load(fh)
+                    prof = tj.get("%s@%dx%dx%d" % (dom_slot, W, H, B))
+                    # (the kernels are bound by vector-instruction issue, not by HBM: the committed PMC passes say how busy the VALUs were)
+                    valu_prof = {k.split("@")[1]: v for k, v in tj.items() if k.startswith("valu_issue@") and k.endswith("@%dx%dx%d" % (W, H, B))} or None
+                except Exception:
+                    prof = None
+            # SURVEY.md 8d's whole-pipeline figure: A = 10*W*H + 48*N + 12*M bytes per pair of a sort-based
+            # matcher whose sort streams through HBM (this build keeps it in LDS: comparable across builds,
+            # not a statement about traffic)
+            a_pair = (10.0 * W * H * B + 48.0 * N_step + 12.0 * M_step) / B
+            roofline = {
+                "bound": "hbm",
+                "kernel": launch_names.get(dom_slot, dom_slot),
+                "achieved": round(achieved, 1),
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4),
+                "traffic": None,
+                "traffic_from_profiles": prof,
+                "valu_issue_from_profiles": valu_prof,
+                "alg_bytes_per_launch": alg.get(dom_slot),
+                "avg_launch_us": round(dom_us, 2),
+                "launches_timed": dom_n,
+                "pipeline_alg_bytes_per_pair": a_pair,
+                "pipeline_alg_GBs_equivalent": round(a_pair * pairs_per_step * args.steps / t_med / 1e9, 1),
+                "pipeline_compulsory_frac": round(sum(alg.values()) * world * args.steps / t_med / 1e9 / HBM_PEAK_GBS, 4),
+                "note": "achieved = bytes the dominant kernel must read + write per launch given its formats (DESIGN.md 4: "
+                        "%s) / mean HIP-event duration of its %d launches inside 40 windows of the headline's steps, on the stream it runs on.  "
+                        "The kernel keeps the reference's sort in LDS and is bound by LDS / issue, not by HBM: `frac` says how "
+                        "far below the HBM roof that leaves it.  `traffic` is not measured by this script; "
+                        "`traffic_from_profiles` = 2*FETCH_SIZE + WRITE_SIZE of the committed rocprofv3 --pmc passes.  "
+                        "pipeline_alg_GBs_equivalent = SURVEY 8d's A*pairs/t: the rate a matcher whose sort streams through HBM "
+                        "would need for this throughput -- NOT traffic and not a fraction of anything (this build's sort never "
+                        "leaves LDS, so it can exceed the peak); pipeline_compulsory_frac = sum of the kernels' compulsory bytes / "
+                        "step time / peak." % (BYTES_TEXT.get(dom_slot, ""), dom_n),
+                "kernels": kinfo,
+            }
 
         # achievable-copy figure of this box: device-to-device copy of 1 GiB, read + write
-        if world == 1 and not args.no_extras:
+        if full and world == 1 and not args.no_extras:
             nb = 1 << 30
             a = torch.empty(nb, dtype=torch.uint8, device=dev)
             b = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -594,14 +657,14 @@ def main():
 
         # the CPU leg: rank 0 only, at any N (after the last collective: the other ranks are done and idle)
         cpu = None
-        if not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             cpu = cpu_baseline(args, W, H)
 
         # A STREAM of batches through the library's two lanes (gpc_hip_set_pipeline(2): batch k+1's k_preprocess and k_hash
         # run beside batch k's join); reported beside the strictly serial headline, whose per-kernel event times and
         # roofline stay clean.  Two output sets alternate (two calls are in flight at a time).
         two = None
-        if world == 1 and P == 1 and not args.no_extras:
+        if full and world == 1 and P == 1 and not args.no_extras:
             c2 = g.Context(dev_index)
             c2.load_forest(args.forest, W, H)
             st2 = torch.cuda.Stream(device=dev)
@@ -625,17 +688,17 @@ def main():
             for _ in range(15):
                 device_sync(); c2.synchronize()
                 t2 = time.perf_counter()
-                for i in range(args.steps):
+                for i in range(xs):
                     step2(i)
                 c2.synchronize()
-                lane_t.append((time.perf_counter() - t2) / args.steps)
+                lane_t.append((time.perf_counter() - t2) / xs)
             dt2 = sorted(lane_t)[len(lane_t) // 2]
             # every pair, every support, both output sets (the arrays were zero-filled; only valid entries are ever written)
             same = bool(all(torch.equal(n, d_counts) and torch.equal(m, d_ncand) and torch.equal(o, d_out) for o, n, m in sets))
             two = {"lanes": 2, "ms_per_step": round(dt2 * 1e3, 4), "value": round(mpix_per_step / dt2, 1),
                    "unit": "Mpix/s", "identical_outputs_all_pairs": same,
                    "note": "gpc_hip_set_pipeline(ctx, 2): consecutive batches alternate between two lanes of ONE context; "
-                           "median of 15 windows of %d steps; not the headline (its kernels overlap, so no clean per-kernel times)" % args.steps}
+                           "median of 15 windows of %d steps; not the headline (its kernels overlap, so no clean per-kernel times)" % xs}
             # the same at 32 pairs per step (a rank's share of configs[3] at 8 GPUs): there the join's fill and drain are a
             # quarter of its launch, which is what the neighbouring batch's kernels fill
             if B >= 32:
@@ -652,10 +715,10 @@ def main():
                 for _ in range(15):
                     device_sync(); c2.synchronize()
                     t2 = time.perf_counter()
-                    for i in range(args.steps):
+                    for i in range(xs):
                         step32(i)
                     c2.synchronize()
-                    lane_t.append((time.perf_counter() - t2) / args.steps)
+                    lane_t.append((time.perf_counter() - t2) / xs)
                 dt32 = sorted(lane_t)[len(lane_t) // 2]
                 same32 = bool(all(torch.equal(n[:32], d_counts[:32]) and torch.equal(m[:32], d_ncand[:32]) and
                                   torch.equal(o[:32], d_out[:32]) and int(n[32:].abs().sum().item()) == 0 for o, n, m in sets))
@@ -668,7 +731,7 @@ def main():
         # BASELINE configs[1] taken literally: ONE pair per step (launch/occupancy-bound, reported
         # beside the batched headline, never instead of it)
         single = None
-        if world == 1 and not args.no_extras:
+        if full and world == 1 and not args.no_extras:
             def step1():
                 ctx.match_batch_device(d_L.data_ptr(), d_R.data_ptr(), W, H, 1, settings, d_outs[-1].data_ptr(), cap,
                                        d_cnts[-1].data_ptr(), d_ncs[-1].data_ptr())
@@ -691,6 +754,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "warmup_steps_run": n_warm,
             "ms_per_step": round(1e3 * t_med / args.steps, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -712,7 +776,7 @@ def main():
             "pairs_per_s": round(pairs_per_step * args.steps / t_med, 1),
             "candidates_per_pair": round(float(allr[:, 1].sum()) / pairs_per_step, 1),
             "supports_per_pair": round(float(allr[:, 2].sum()) / pairs_per_step, 1),
-            "verified_vs_oracle": None if args.no_verify else True,
+            "verified_vs_oracle": True if (full and not args.no_verify) else None,
             "verified_pairs": int(allr[:, 4].sum()),
             "roofline": roofline,
             "cpu_baseline": cpu,
@@ -729,7 +793,7 @@ def main():
             strong["efficiency_vs_n_times_one_gpu_256_pairs"] = round(strong["value"] / value, 4)
         if share8_windows:
             s8 = sorted(share8_windows)
-            t8 = s8[len(s8) // 2] / args.steps
+            t8 = s8[len(s8) // 2] / xs
             line["strong_256_share_at_8_gpus"] = {
                 "pairs_per_step": 32, "ms_per_step": round(t8 * 1e3, 4), "value": round(2.0 * W * H * 32 / t8 / 1e6, 1), "unit": "Mpix/s",
                 "fraction_of_the_256_pair_rate": round(2.0 * W * H * 32 / t8 / 1e6 / value, 4),

@@ -220,7 +220,7 @@ def test_rccl_path_rehearsal_on_one_gpu(tmp_path):
                MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
                           "--windows", "3", "--batch", "16", "--verify-pairs", "3", "--no-cpu-baseline", "--no-extras",
-                          "--host-path"],
+                          "--host-path", "--full"],
                          env=env, check=True, capture_output=True, text=True, timeout=600).stdout
     line = json.loads(out.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["steps"] == 3 and line["windows"]["count"] == 3
@@ -243,7 +243,7 @@ def test_bench_gpus_2_plainly_starts_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_PORT")}
     env.update(GPC_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", GPC_BENCH_NO_SINGLE="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--windows", "3", "--batch", "16", "--verify-pairs", "3", "--cpu-seconds", "1"],
+                        "--windows", "3", "--batch", "16", "--verify-pairs", "3", "--cpu-seconds", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]

@@ -8,10 +8,11 @@ import numpy as np
 import pytest
 
 from oracle.pyoracle import SPLIT_DTYPE
-from test_host_api import BIN, ROOT, compile_cpp, run
+from test_host_api import BIN, ROOT, compile_cpp, linked_libs, run
 from test_training import make_triplets, stats_equal
 
-REF_TRAIN = "/root/reference/samples/train.cpp"
+# the reference's own samples/train.cpp, compiled by build() (oracle/Makefile, target `ref`)
+REF_TRAIN_ON_AMD = os.path.join(ROOT, "oracle", "_ref", "ref_train_on_amd_headers")
 
 
 @pytest.fixture(scope="module")
@@ -43,10 +44,11 @@ def test_patch_extraction_and_file_round_trip(train_bin, tmp_path):
     assert os.path.getsize(str(tmp_path / "t.bin")) == 3 * 729
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TRAIN), reason="reference tree not present")
-def test_reference_train_sample_compiles_against_these_headers(tmp_path):
+@pytest.mark.skipif(not os.path.exists(REF_TRAIN_ON_AMD), reason="oracle/_ref not built (no reference tree)")
+def test_reference_train_sample_compiles_against_these_headers():
     """The reference's own samples/train.cpp, compiled where it lies against include/gpc/training.hpp."""
-    compile_cpp(REF_TRAIN, str(tmp_path / "ref_train_on_amd_headers"))
+    assert os.access(REF_TRAIN_ON_AMD, os.X_OK)
+    assert "libgpc_hip.so" in linked_libs(REF_TRAIN_ON_AMD)
 
 
 @pytest.mark.gpu

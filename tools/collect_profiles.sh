@@ -10,8 +10,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_bench && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python3 $R/bench.py --no-cpu-baseline --no-extras --windows 20 > $O/prof_bench.json 2> $O/prof_bench.err; cp $(find /tmp/prof_bench -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv ); echo "rocprof rc=$?"
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_bench && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python3 $R/bench.py --full --no-cpu-baseline --no-extras --windows 20 > $O/prof_bench.json 2> $O/prof_bench.err; cp $(find /tmp/prof_bench -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv ); echo "rocprof rc=$?"
 ( cd /tmp && export TMPDIR=/tmp && bash $R/tools/pmc_collect.sh $O/pmc 3 256 > $O/pmc.log 2>&1 ); tail -1 $O/pmc.log
 python tools/make_traffic.py $O/pmc ${TAG} 1024 436 256 > $O/traffic.txt 2>&1
 cp profiles/traffic.json $O/traffic.json; cp profiles/${TAG%%_*}_pmc/${TAG}_pmc_summary.json $O/ 2>/dev/null
