@@ -4,7 +4,7 @@
 // exposes: Point / Descriptor / Support / Correspondence (buffer.hpp:52-102), RGBColor
 // (:41-50), Buffer<T> (:142-193: row-major, columns padded to a multiple of 16, public
 // width/height), clearBoundary (:630-654), PNG read/write (:197-474) and the KITTI-colour
-// disparity overlay (:949-1014).  Same names, argument meaning and error behaviour
+// disparity overlay (:949-1014), RGBBuffer (:772-875).  Same names, argument meaning and error behaviour
 // (messages on stdout, sentinel return values); storage is a vector, zero-initialised by the public constructors (the
 // reference's Eigen arrays are not initialised at all; Buffer::uninitialized gives the library's own outputs the same).
 #ifndef GPC_AMD_NDB_BUFFER_HPP
@@ -254,6 +254,45 @@ inline Buffer<RGBColor> Buffer<T>::convertToRGB() const {
     }
   return out;
 }
+
+// buffer.hpp:772-875: an RGB image (Sintel stereo disparities are RGB PNGs).  readPNGRGB keeps 8-bit RGB as it is (row-major,
+// columns padded to a multiple of 16); gray and 16-bit images leave the pixels as they were and still return 0, like the
+// reference; other colour types are refused with its message.  0 = ok, 1 = error.
+class RGBBuffer : public Buffer<RGBColor> {
+ public:
+  RGBBuffer() {}
+  int readPNGRGB(std::string filename) {
+    pngio::Image img;
+    const int rc = pngio::decode_file(filename, img);
+    if (rc == 1) {
+      std::cout << "ERR: File" << filename << " could not be opened for reading" << std::endl;
+      return 1;
+    }
+    if (rc == 2) {
+      std::cout << "ERR: File" << filename << " is not recognized as a PNG file" << std::endl;
+      return 1;
+    }
+    if (rc != 0) {
+      std::cout << "ERR: Error during read_image" << std::endl;
+      return 1;
+    }
+    width = img.width;
+    height = img.height;
+    resize(height, width);
+    if (img.bit_depth == 8 && img.color_type == 2)
+      for (int y = 0; y < height; ++y) {
+        const uint8_t* row = &img.pixels[(size_t)y * width * 3];
+        for (int x = 0; x < width; ++x) (*this)(y, x) = RGBColor(row[3 * x], row[3 * x + 1], row[3 * x + 2]);
+      }
+    conservativeResize(height, align16(width));
+    if (!(img.color_type == 0 || img.color_type == 2)) {
+      std::cout << "ERR: found something other than gray or 3 channel color image(" << img.color_type << ") aborting!"
+                << std::endl;
+      return 1;
+    }
+    return 0;
+  }
+};
 
 // Piecewise-linear KITTI colour ramp as used by getDisparityVisualization (buffer.hpp:958-1010):
 // value in [0, 0.8] -> RGB.  Kept in the same float arithmetic so the bytes are identical.

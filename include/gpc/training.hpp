@@ -2,9 +2,8 @@
 // ForestSettings and Forest::trainAndExport (bootstrap of the training set per fern, Fern::train on
 // the GPU, export in the text format Forest::readForest reads).
 //
-// The Sintel dataset readers of the reference (SintelOpticalFlow.hpp, SintelStereo.hpp: PNG / flow
-// file walking and keypoint selection) are outside this build; gpc::datasource::SintelOpticalFlow
-// offers only loadTrainingData(), which is all samples/train.cpp needs.
+// The Sintel datasources of the reference (gpc::datasource::SintelOpticalFlow, SintelStereo) are in
+// gpc/SintelOpticalFlow.hpp and gpc/SintelStereo.hpp, included here as the reference does.
 #ifndef _GPC_training
 #define _GPC_training
 #include <sys/stat.h>
@@ -19,28 +18,11 @@
 
 #include "gpc/Feature.hpp"
 #include "gpc/Fern.hpp"
+#include "gpc/SintelOpticalFlow.hpp"
+#include "gpc/SintelStereo.hpp"
 #include "gpc/buffer.hpp"
 
 namespace gpc {
-namespace datasource {
-// SintelOpticalFlow.hpp:181-190
-class SintelOpticalFlow {
-  typedef gpc::training::Feature::GPCPatchTriplet GPCTriplet_t;
-  gpc::training::Feature Feature;
-
- public:
-  std::vector<GPCTriplet_t> loadTrainingData(std::string path) {
-    struct stat buffer;
-    if (stat(path.c_str(), &buffer) != 0) {
-      std::vector<GPCTriplet_t> emptyset;
-      cout << "ERR: No extracted training set found at given path" << endl;
-      return emptyset;
-    } else {
-      return Feature.loadAllTriplets(path);
-    }
-  }
-};
-}  // namespace datasource
 
 namespace training {
 // training.hpp:59-74

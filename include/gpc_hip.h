@@ -334,6 +334,42 @@ int gpc_hip_train_eval_level(gpc_hip_ctx* ctx, gpc_hip_train_set* set, const gpc
                              int taulo, int tauhi, int32_t* tp, int32_t* fp, int32_t* tot);
 int gpc_hip_train_commit_level(gpc_hip_ctx* ctx, gpc_hip_train_set* set, const gpc_split* best, int mark_split);
 
+/* ---- training-set extraction ---------------------------------------------------- */
+/* One triplet of keypoints: the reference point in the LEFT frame, the positive and the negative point in the RIGHT
+ * frame (the kptsL / kptsR / kptsN lists of SintelOpticalFlow.hpp:487-489 and SintelStereo.hpp:396-398). */
+typedef struct gpc_triplet_points {
+  int32_t rx, ry, px, py, nx, ny;
+} gpc_triplet_points;
+
+/* Feature::extractAllTriplets (Feature.hpp:191-245) for `nframes` frame pairs, straight into a device training set.
+ *   rawL, rawR   [nframes][height][width] raw 8-bit frames (host memory here, HBM for the _device form);
+ *   pts          the triplets of all frames back to back, frame f's at [frame_first[f], frame_first[f + 1]);
+ *   frame_first  nframes + 1 ascending offsets, frame_first[0] = 0.
+ * Smoothing is the `smooth` output of preprocessImage (3x3 box + clearBoundary, inference.hpp:306-313) in the context's
+ * arithmetic (gpc_hip_set_arithmetic).  A triplet is KEPT when all three points satisfy x > 20 && y > 20 && x < width-20
+ * && y < height-20 (Feature.hpp:208-214); kept triplets are numbered in frame order, then point order.  Patch bytes are
+ * those of getPatch(.., x, y, 27) (buffer.hpp:534-544): byte 27 * ix + iy = pixel (x + ix - 13, y + iy - 13).
+ * order == NULL: kept triplet k becomes triplet k of the set; otherwise it becomes triplet order[k], and `order` must be a
+ * permutation of 0 .. n_kept-1 -- how a caller applies the reference's final std::random_shuffle (SintelOpticalFlow.hpp:160,
+ * SintelStereo.hpp:152) without a host copy of the set.
+ * The result is an ordinary training set with all marks cleared (every gpc_hip_train_* call takes it); *n_kept = its size.
+ * Nothing kept: GPC_OK, *n_kept = 0, *out = NULL.  GPC_E_INVALID for null pointers, width % 16, descending frame_first and
+ * an order that is not a permutation (which must hold n_kept entries: the caller computes n_kept with the keep rule
+ * above).  The frames are processed in chunks (64 MiB of smoothed frames by default), so the
+ * device workspace stays bounded however many frames there are.  Synchronous. */
+int gpc_hip_extract_triplets(gpc_hip_ctx* ctx, const uint8_t* rawL, const uint8_t* rawR, int width, int height,
+                             int nframes, const gpc_triplet_points* pts, const int32_t* frame_first,
+                             const int32_t* order, gpc_hip_train_set** out, int* n_kept);
+/* The same with rawL / rawR in HBM ([nframes][height][width] each); pts, frame_first and order stay in host memory.
+ * Frames that are not device memory of the context's GPU (checked at their first and last byte) are refused with
+ * GPC_E_INVALID before anything is launched.  The chunk workspaces of both forms are released before the call returns. */
+int gpc_hip_extract_triplets_device(gpc_hip_ctx* ctx, const uint8_t* d_rawL, const uint8_t* d_rawR, int width, int height,
+                                    int nframes, const gpc_triplet_points* pts, const int32_t* frame_first,
+                                    const int32_t* order, gpc_hip_train_set** out, int* n_kept);
+/* The inverse of gpc_hip_train_set_create's layout: triplets [first, first + n) of the set into `aos`, n * 3 * 729 bytes in
+ * the byte order of Feature::storeAllTriplets (Feature.hpp:254-263).  Synchronous. */
+int gpc_hip_train_set_read(gpc_hip_ctx* ctx, gpc_hip_train_set* set, int first, int n, uint8_t* aos);
+
 /* ---- measurement -------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the context's stream.  When enabled every launch of
  * the named kernels is bracketed by hipEvents; gpc_hip_kernel_time returns the summed

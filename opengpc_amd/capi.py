@@ -81,6 +81,7 @@ SYMBOLS = [
     "gpc_hip_train_set_create", "gpc_hip_train_set_destroy", "gpc_hip_train_set_size", "gpc_hip_train_set_marks",
     "gpc_hip_train_eval_split", "gpc_hip_train_mark_split_samples", "gpc_hip_train_fern",
     "gpc_hip_train_begin_fern", "gpc_hip_train_eval_level", "gpc_hip_train_commit_level",
+    "gpc_hip_extract_triplets", "gpc_hip_extract_triplets_device", "gpc_hip_train_set_read",
 ]
 
 
@@ -162,6 +163,9 @@ def load():
     L.gpc_hip_train_begin_fern.argtypes = [vp, vp, ci]
     L.gpc_hip_train_eval_level.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
     L.gpc_hip_train_commit_level.argtypes = [vp, vp, vp, ci]
+    L.gpc_hip_extract_triplets.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+    L.gpc_hip_extract_triplets_device.argtypes = L.gpc_hip_extract_triplets.argtypes
+    L.gpc_hip_train_set_read.argtypes = [vp, vp, ci, ci, vp]
     _lib = L
     return L
 
@@ -206,10 +210,55 @@ SPLIT_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("tau", "<i4")])
 STATS_DTYPE = np.dtype([("prec", "<f8"), ("rec", "<f8"), ("hmean", "<f8"), ("convcomb", "<f8"),
                         ("tp", "<i4"), ("fp", "<i4"), ("fn", "<i4"), ("tot", "<i4")])
 PATCH_BYTES = 729
+# gpc_triplet_points: the reference point in the left frame, the positive and the negative point in the right frame
+POINTS_DTYPE = np.dtype([("rx", "<i4"), ("ry", "<i4"), ("px", "<i4"), ("py", "<i4"), ("nx", "<i4"), ("ny", "<i4")])
 
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def kept_count(pts, width, height):
+    """triplets that gpc_hip_extract_triplets keeps: all three points x > 20 && y > 20 && x < width-20 && y < height-20
+    (Feature.hpp:208-214)"""
+    p = np.asarray(pts, POINTS_DTYPE)
+    ok = np.ones(len(p), bool)
+    for x, y in (("rx", "ry"), ("px", "py"), ("nx", "ny")):
+        ok &= (p[x] > 20) & (p[y] > 20) & (p[x] < width - 20) & (p[y] < height - 20)
+    return int(ok.sum())
+
+
+def _device_frames(a, b, device):
+    """True for torch.uint8 tensors on GPU `device` (the _device entry point reads them where they lie); False for host
+    frames.  Tensors on another GPU, of another dtype or not contiguous are refused: the kernels would read them as raw
+    bytes, or fault on an address the GPU cannot reach."""
+    ta, tb = hasattr(a, "data_ptr") and hasattr(a, "is_cuda"), hasattr(b, "data_ptr") and hasattr(b, "is_cuda")
+    if not (ta or tb):
+        return False
+    if not (ta and tb):
+        raise ValueError("rawL / rawR: both tensors or both arrays")
+    import torch
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise ValueError("rawL / rawR: torch.uint8 tensors (got %s, %s)" % (a.dtype, b.dtype))
+    if a.is_cuda != b.is_cuda:
+        raise ValueError("rawL / rawR: both on the GPU or both on the host")
+    if not a.is_cuda:
+        return False
+    if a.device.index != device or b.device.index != device:
+        raise ValueError("rawL / rawR: tensors on cuda:%d, the context's device (got %s, %s)" % (device, a.device, b.device))
+    if not (a.is_contiguous() and b.is_contiguous()):
+        raise ValueError("rawL / rawR: contiguous tensors")
+    return True
+
+
+def _host_frames(a):
+    """uint8 host frames as a C-contiguous numpy array (CPU tensors included); other dtypes are refused, not converted"""
+    if hasattr(a, "data_ptr") and hasattr(a, "numpy"):
+        a = a.detach().numpy()
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        raise ValueError("rawL / rawR: uint8 frames (got %s)" % a.dtype)
+    return np.ascontiguousarray(a)
 
 
 _live_contexts = weakref.WeakSet()
@@ -463,6 +512,51 @@ class Context:
         """Uploads (n, 3, 729) uint8 patch triplets (ref, pos, neg); returns a TrainSet."""
         return TrainSet(self, triplets)
 
+    def extract_triplets(self, rawL, rawR, pts, frame_first, order=None):
+        """Feature::extractAllTriplets for a batch of frame pairs (gpc_hip_extract_triplets), straight into a TrainSet.
+        rawL, rawR: (nframes, H, W) uint8 numpy arrays or CPU tensors (host entry point), or contiguous torch.uint8 tensors
+        on this context's GPU (the _device entry point; a tensor on another device is refused); pts: POINTS_DTYPE records
+        (or an (n, 6) int array) of all frames back to back; frame_first: nframes + 1 ascending offsets into pts, the last
+        one len(pts); order: None or a permutation of the kept triplets.  Returns None when no triplet is kept.
+        Anything else raises ValueError before the library is called: the C entry points trust these lengths."""
+        dev = _device_frames(rawL, rawR, self.device)
+        if dev:
+            if rawL.shape != rawR.shape or rawL.dim() != 3:
+                raise ValueError("rawL / rawR: (nframes, H, W) tensors of one shape")
+            nframes, H, W = rawL.shape
+            pL, pR = C.c_void_p(rawL.data_ptr()), C.c_void_p(rawR.data_ptr())
+            fn = self.L.gpc_hip_extract_triplets_device
+        else:
+            rawL, rawR = _host_frames(rawL), _host_frames(rawR)
+            if rawL.ndim != 3 or rawL.shape != rawR.shape:
+                raise ValueError("rawL / rawR: (nframes, H, W) arrays of one shape")
+            nframes, H, W = rawL.shape
+            pL, pR = _ptr(rawL), _ptr(rawR)
+            fn = self.L.gpc_hip_extract_triplets
+        p = np.asarray(pts)
+        if p.dtype != POINTS_DTYPE:
+            p = np.ascontiguousarray(p, np.int32)
+            if p.size % 6:
+                raise ValueError("pts: six coordinates per triplet")
+            p = p.reshape(-1, 6).view(POINTS_DTYPE).reshape(-1)
+        p = np.ascontiguousarray(p).reshape(-1)
+        ff = np.ascontiguousarray(frame_first, np.int32).reshape(-1)
+        if len(ff) != nframes + 1 or ff[0] != 0 or (np.diff(ff) < 0).any() or ff[-1] != len(p):
+            raise ValueError("frame_first: nframes + 1 ascending offsets from 0 to len(pts)")
+        o = None
+        if order is not None:
+            o = np.ascontiguousarray(order, np.int32).reshape(-1)
+            n_kept = kept_count(p, W, H)
+            if len(o) != n_kept:
+                raise ValueError("order: %d entries for %d kept triplets" % (len(o), n_kept))
+        h = C.c_void_p()
+        n = C.c_int()
+        self._ck(fn(self.h, pL, pR, int(W), int(H), int(nframes), _ptr(p) if len(p) else None, _ptr(ff), _ptr(o),
+                    C.byref(h), C.byref(n)))
+        if n.value == 0:
+            return None
+        return TrainSet(self, handle=h, n=n.value)
+
     # ---- measurement
     def enable_kernel_timing(self, on=True, only=None):
         """HIP-event bracketing of kernel launches; `only` = iterable of kernel names to restrict it to."""
@@ -497,15 +591,26 @@ class TrainSet:
     """Device-resident training triplets of one Context (gpc_hip_train_set): Fern::evalSplit,
     Fern::markSplitSamples and Fern::train (with caller-supplied hyperplane samples) on the GPU."""
 
-    def __init__(self, ctx, triplets):
+    def __init__(self, ctx, triplets=None, handle=None, n=0):
+        self.ctx = ctx
+        if handle is not None:  # a set the library made (Context.extract_triplets)
+            self.n = int(n)
+            self.h = handle
+            return
         t = np.ascontiguousarray(triplets, np.uint8)
         if t.ndim != 3 or t.shape[1:] != (3, PATCH_BYTES):
             raise ValueError("triplets must have shape (n, 3, 729)")
-        self.ctx = ctx
         self.n = len(t)
         h = C.c_void_p()
         ctx._ck(ctx.L.gpc_hip_train_set_create(ctx.h, _ptr(t), self.n, C.byref(h)))
         self.h = h
+
+    def read(self, first=0, n=None):
+        """Triplets [first, first + n) as an (n, 3, 729) uint8 array (gpc_hip_train_set_read)."""
+        n = self.n - first if n is None else int(n)
+        out = np.empty((max(n, 0), 3, PATCH_BYTES), np.uint8)
+        self.ctx._ck(self.ctx.L.gpc_hip_train_set_read(self.ctx.h, self.h, int(first), n, _ptr(out)))
+        return out
 
     def close(self):
         if self.h and self.ctx.h:

@@ -10,6 +10,7 @@
 #endif
 #include <sched.h>
 
+#include <algorithm>
 #include <cctype>
 #include <condition_variable>
 #include <cstdio>
@@ -25,6 +26,7 @@
 #include <vector>
 
 #include "gpc_device.h"
+#include "k_extract.h"
 #include "k_global.h"
 #include "k_hash.h"
 #include "k_hashtable.h"
@@ -271,6 +273,10 @@ struct gpc_hip_ctx {
   std::vector<TimedSpan> free_spans;
 
   std::vector<gpc_hip_train_set*> train_sets;  // training sets created on this context
+  // gpc_hip_extract_triplets: raw (host entry only), smooth and grad of one chunk of frame pairs, the chunk's column groups
+  // (allocated by the call, released before it returns)
+  DevBuf ext_raw, ext_smooth, ext_grad, ext_groups;
+  int extract_frames = 0;     // GPC_HIP_EXTRACT_FRAMES: frame pairs per chunk (tests; default: 64 MiB of smoothed frames)
 
   // Forest::preprocessImage -> Forest::rectifiedMatch without the round trip (the reference's PreprocessedImage travels by
   // value through host memory, inference.hpp:161-165): the last two preprocessed images stay on the device beside the
@@ -1930,6 +1936,10 @@ int gpc_hip_create(int device, gpc_hip_ctx** out) {
     const int v = atoi(e);
     if (v >= 0 && v <= 2) c->resident_mode = v;
   }
+  if (const char* e = getenv("GPC_HIP_EXTRACT_FRAMES")) {
+    const int v = atoi(e);
+    if (v >= 1) c->extract_frames = v;
+  }
   c->debug = getenv("GPC_HIP_DEBUG") != nullptr;
   c->debug_plan = getenv("GPC_HIP_DEBUG_PLAN") != nullptr;
   c->num_cus = prop.multiProcessorCount;
@@ -1961,7 +1971,7 @@ int gpc_hip_destroy(gpc_hip_ctx* c) {
                     &c->stats, &c->out, &c->counts, &c->ncand, &c->mask, &c->gkeys[0], &c->gkeys[1],
                     &c->gvals[0], &c->gvals[1], &c->ghist, &c->gmisc, &c->hkeys[0], &c->hkeys[1],
                     &c->hvals[0], &c->hvals[1], &c->hrec, &c->forest_dev, &c->packed, &c->gpart, &c->jstate, &c->gkv,
-                    &c->res_smooth, &c->res_grad};
+                    &c->res_smooth, &c->res_grad, &c->ext_raw, &c->ext_smooth, &c->ext_grad, &c->ext_groups};
   while (!c->train_sets.empty()) (void)gpc_hip_train_set_destroy(c, c->train_sets.back());
   for (DevBuf* b : bufs) release(*b);
   for (auto& s : c->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -3561,6 +3571,217 @@ int gpc_hip_train_fern(gpc_hip_ctx* c, gpc_hip_train_set* t, int max_depth, cons
     level_stats[level] = stats;                                             // what train() prints        :357
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GPC_OK;
+}
+
+// ------------------------------------------------------------------ training-set extraction
+
+// Feature::extractAllTriplets (Feature.hpp:191-245) for a batch of frame pairs, straight into a device training set
+// (k_extract.h).  The keep rule depends on the points alone, so the host decides which triplets stay and where each goes
+// (column order[k] of kept triplet k, or k); the frames are smoothed chunk by chunk -- run_preprocess, the `smooth` output
+// of preprocessImage in the context's arithmetic -- and each chunk's kernel gathers the patches of its own columns.
+// The frames handed to the _device entry point must be device memory of the context's GPU, first byte and last: a host
+// address (pageable memory, a CPU tensor) would make the kernels fault.
+static bool on_this_device(const gpc_hip_ctx* c, const uint8_t* p, size_t bytes) {
+  for (const uint8_t* q : {p, p + bytes - 1}) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, q) != hipSuccess) {
+      (void)hipGetLastError();  // pageable host memory: not an error of this library
+      return false;
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != c->device) return false;
+  }
+  return true;
+}
+
+static int extract_triplets(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, bool on_device, int W, int H, int nframes,
+                            const gpc_triplet_points* pts, const int32_t* frame_first, const int32_t* order,
+                            gpc_hip_train_set** out, int* n_kept) {
+  if (out) *out = nullptr;
+  if (n_kept) *n_kept = 0;
+  if (!c || !rawL || !rawR || !frame_first || !out || !n_kept || nframes < 0) return GPC_E_INVALID;
+  CHK(check_dims(W, H));
+  if (frame_first[0] != 0) return GPC_E_INVALID;
+  for (int f = 0; f < nframes; ++f)
+    if (frame_first[f + 1] < frame_first[f]) return GPC_E_INVALID;
+  const int total = frame_first[nframes];
+  if (total > 0 && !pts) return GPC_E_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (on_device && nframes > 0) {
+    const size_t bytes = (size_t)nframes * W * H;
+    if (!on_this_device(c, rawL, bytes) || !on_this_device(c, rawR, bytes)) {
+      snprintf(c->err, sizeof(c->err), "gpc_hip_extract_triplets_device: the frames are not device memory of device %d", c->device);
+      return GPC_E_INVALID;
+    }
+  }
+  // Feature.hpp:208-214: all three points more than 20 px inside the image
+  auto inside = [W, H](int x, int y) { return x > 20 && y > 20 && x < W - 20 && y < H - 20; };
+  std::vector<int32_t> kept, kept_frame;
+  for (int f = 0; f < nframes; ++f)
+    for (int k = frame_first[f]; k < frame_first[f + 1]; ++k) {
+      const gpc_triplet_points& p = pts[k];
+      if (inside(p.rx, p.ry) && inside(p.px, p.py) && inside(p.nx, p.ny)) {
+        kept.push_back(k);
+        kept_frame.push_back(f);
+      }
+    }
+  const int n = (int)kept.size();
+  std::vector<int32_t> col_src(n);  // column -> kept index
+  if (order) {
+    std::vector<uint8_t> seen(n, 0);
+    for (int k = 0; k < n; ++k) {
+      const int32_t o = order[k];
+      if (o < 0 || o >= n || seen[o]) return GPC_E_INVALID;
+      seen[o] = 1;
+      col_src[o] = k;
+    }
+  } else {
+    for (int k = 0; k < n; ++k) col_src[k] = k;
+  }
+  if (n == 0) return GPC_OK;
+
+  // chunks of frame pairs: 64 MiB of smoothed frames by default (pixel offsets of a chunk stay below 2^31)
+  const size_t npx = (size_t)W * H;
+  int per_chunk = c->extract_frames;
+  if (per_chunk <= 0) per_chunk = (int)std::max<size_t>(1, (size_t(64) << 20) / (2 * npx));
+  per_chunk = (int)std::max<size_t>(1, std::min<size_t>(per_chunk, (size_t(1) << 31) / (2 * npx)));
+  const int nchunks = (nframes + per_chunk - 1) / per_chunk;
+  const long np = ((long)n + 255) / 256 * 256;
+  // column groups per chunk: a group of four columns goes to every chunk one of its columns comes from; padding columns
+  // (n .. np) are zeroed by whichever record holds them, groups of padding only by the chunk of the last triplet
+  std::vector<std::vector<gpc::ExGroup>> work(nchunks);
+  const int last_chunk = kept_frame[col_src[n - 1]] / per_chunk;
+  for (long q = 0; q < np / 4; ++q) {
+    int ch[4];
+    for (int b = 0; b < 4; ++b) {
+      const long col = 4 * q + b;
+      ch[b] = col < n ? kept_frame[col_src[col]] / per_chunk : -1;
+    }
+    for (int b = 0; b < 4; ++b) {
+      const int mine = ch[b] >= 0 ? ch[b] : (ch[0] < 0 && b == 0 ? last_chunk : -1);
+      if (mine < 0) continue;
+      bool first = true;  // one record per (group, chunk)
+      for (int b2 = 0; b2 < b; ++b2)
+        if (ch[b2] == ch[b] && ch[b] >= 0) first = false;
+      if (!first) continue;
+      gpc::ExGroup g;
+      g.q = (int32_t)q;
+      for (int b2 = 0; b2 < 4; ++b2) {
+        const long col = 4 * q + b2;
+        if (col >= n) {
+          for (int p = 0; p < 3; ++p) g.off[4 * p + b2] = EX_ZERO;
+        } else if (ch[b2] != mine) {
+          for (int p = 0; p < 3; ++p) g.off[4 * p + b2] = EX_KEEP;
+        } else {
+          const int k = col_src[col];
+          const gpc_triplet_points& t = pts[kept[k]];
+          const long fl = kept_frame[k] - (long)mine * per_chunk;
+          // smooth of the chunk: [frame][side][H][W]; top-left pixel of the 27x27 patch
+          g.off[4 * 0 + b2] = (int32_t)(((2 * fl + 0) * H + t.ry - 13) * (long)W + t.rx - 13);
+          g.off[4 * 1 + b2] = (int32_t)(((2 * fl + 1) * H + t.py - 13) * (long)W + t.px - 13);
+          g.off[4 * 2 + b2] = (int32_t)(((2 * fl + 1) * H + t.ny - 13) * (long)W + t.nx - 13);
+        }
+      }
+      work[mine].push_back(g);
+    }
+  }
+
+  gpc_hip_train_set* t = new gpc_hip_train_set();
+  t->owner = c;
+  t->n = n;
+  t->np = np;
+  // the chunk workspaces (smoothed frames, the gradient image run_preprocess also writes, uploaded frames, column groups:
+  // about 4 x 64 MiB at the default chunk size) are given back when the call ends; the page-locked transfer arena is the
+  // context's, shared with the other host-buffer entry points, and stays
+  auto release_ws = [c]() {
+    release(c->ext_raw);
+    release(c->ext_smooth);
+    release(c->ext_grad);
+    release(c->ext_groups);
+  };
+  auto fail = [&](int st) {
+    (void)hipStreamSynchronize(c->stream);
+    release_ws();
+    if (t->planes) (void)hipFree(t->planes);
+    if (t->flags) (void)hipFree(t->flags);
+    delete t;
+    return st;
+  };
+  if (hipMalloc((void**)&t->planes, (size_t)3 * TS_PATCH * np) != hipSuccess || hipMalloc((void**)&t->flags, (size_t)np) != hipSuccess) {
+    snprintf(c->err, sizeof(c->err), "training set of %d triplets: device allocation failed", n);
+    return fail(GPC_E_HIP);
+  }
+  const bool bits_before = c->grad_is_bits;  // (run_preprocess records what kind of gradient image c->grad holds)
+  for (int ch = 0; ch < nchunks; ++ch) {
+    const std::vector<gpc::ExGroup>& gl = work[ch];
+    if (gl.empty()) continue;  // no triplet of these frames is kept: they are not even smoothed
+    const int f0 = ch * per_chunk, nf = std::min(per_chunk, nframes - f0);
+    const size_t side_bytes = npx * nf, group_bytes = pad16(sizeof(gpc::ExGroup) * gl.size());
+    int st = GPC_OK;
+    uint8_t* d_arena = nullptr;
+    // the page-locked arena carries the chunk's column groups (and, from host memory, its frames): the previous chunk's
+    // copies out of it must be done before it is written again
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(GPC_E_HIP);
+    if ((st = xfer_reserve(c, group_bytes + (on_device ? 0 : 2 * side_bytes), &d_arena)) != GPC_OK) return fail(st);
+    if ((st = ensure(c, c->ext_smooth, 2 * side_bytes)) != GPC_OK || (st = ensure(c, c->ext_grad, 2 * side_bytes)) != GPC_OK ||
+        (st = ensure(c, c->ext_groups, group_bytes)) != GPC_OK)
+      return fail(st);
+    memcpy(c->h_xfer, gl.data(), sizeof(gpc::ExGroup) * gl.size());
+    const uint8_t *d_L = rawL + f0 * npx, *d_R = rawR + f0 * npx;
+    if (!on_device) {
+      if ((st = ensure(c, c->ext_raw, 2 * side_bytes)) != GPC_OK) return fail(st);
+      memcpy(c->h_xfer + group_bytes, rawL + f0 * npx, side_bytes);
+      memcpy(c->h_xfer + group_bytes + side_bytes, rawR + f0 * npx, side_bytes);
+      if ((st = dev_copy16(c, c->ext_raw.p, d_arena + group_bytes, 2 * side_bytes)) != GPC_OK) return fail(st);
+      d_L = (const uint8_t*)c->ext_raw.p;
+      d_R = d_L + side_bytes;
+    }
+    if ((st = dev_copy16(c, c->ext_groups.p, d_arena, group_bytes)) != GPC_OK) return fail(st);
+    st = run_preprocess(c, d_L, d_R, W, H, nf, 2, 10, false, (uint8_t*)c->ext_smooth.p, (uint8_t*)c->ext_grad.p);
+    c->grad_is_bits = bits_before;
+    if (st != GPC_OK) return fail(st);
+    const unsigned nblk = (unsigned)((gl.size() + EX_GROUPS - 1) / EX_GROUPS);
+    hipLaunchKernelGGL(gpc::k_extract_gather, dim3(nblk, 3, 3), dim3(TS_THREADS), 0, c->stream, (const uint8_t*)c->ext_smooth.p, W,
+                       (const gpc::ExGroup*)c->ext_groups.p, (int)gl.size(), np, t->planes);
+    if (hipGetLastError() != hipSuccess) return fail(GPC_E_HIP);
+  }
+  if (hipMemsetAsync(t->flags, 0, (size_t)np, c->stream) != hipSuccess) return fail(GPC_E_HIP);
+  hipLaunchKernelGGL(gpc::k_ts_begin, dim3((unsigned)(np / TS_THREADS)), dim3(TS_THREADS), 0, c->stream, t->flags, n, np, 1);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return fail(GPC_E_HIP);
+  release_ws();
+  c->train_sets.push_back(t);
+  *out = t;
+  *n_kept = n;
+  return GPC_OK;
+}
+
+int gpc_hip_extract_triplets(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, int W, int H, int nframes,
+                             const gpc_triplet_points* pts, const int32_t* frame_first, const int32_t* order,
+                             gpc_hip_train_set** out, int* n_kept) {
+  return extract_triplets(c, rawL, rawR, false, W, H, nframes, pts, frame_first, order, out, n_kept);
+}
+
+int gpc_hip_extract_triplets_device(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H, int nframes,
+                                    const gpc_triplet_points* pts, const int32_t* frame_first, const int32_t* order,
+                                    gpc_hip_train_set** out, int* n_kept) {
+  return extract_triplets(c, d_rawL, d_rawR, true, W, H, nframes, pts, frame_first, order, out, n_kept);
+}
+
+int gpc_hip_train_set_read(gpc_hip_ctx* c, gpc_hip_train_set* t, int first, int n, uint8_t* aos) {
+  CHK(train_check(c, t));
+  if (first < 0 || n < 0 || (long)first + n > t->n || (n > 0 && !aos)) return GPC_E_INVALID;
+  const int step = 16384;  // triplets per pass through the page-locked arena (36 MB)
+  for (int done = 0; done < n; done += step) {
+    const int m = std::min(step, n - done);
+    const size_t bytes = (size_t)m * 3 * TS_PATCH;
+    uint8_t* d_arena = nullptr;
+    CHK(xfer_reserve(c, bytes, &d_arena));
+    hipLaunchKernelGGL(gpc::k_ts_read, dim3((unsigned)((m + 63) / 64), 3, 3), dim3(TS_THREADS), 0, c->stream, (const uint8_t*)t->planes,
+                       t->np, first + done, m, d_arena);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(aos + (size_t)done * 3 * TS_PATCH, c->h_xfer, bytes);
+  }
   return GPC_OK;
 }
 
