@@ -93,6 +93,8 @@ struct ContextHolder {
   size_t support_hint = 0;  // supports of this thread's last matchPair call (+ slack): how large the next result array starts
   gpc_filter_mask warmed;   // the forest (with its image size) readForest last warmed this thread's context for
   bool have_warmed = false;
+  std::vector<gpc_filter_mask> uploaded_groups;  // the groups last uploaded (group mode; `have` is false then)
+  std::vector<gpc_filter_mask> warmed_groups;
   ~ContextHolder() {
     if (ctx) gpc_hip_destroy(ctx);
   }
@@ -191,6 +193,75 @@ class Forest {
     FilterMask result = fm.type == 0 ? FilterMask(mask, width, height, 0) : FilterMask(mask, tau, width, height, 1);
     if (st == GPC_OK && fm.num_tests > 0 && !std::getenv("GPC_HIP_NO_WARMUP")) warmUp(result);
     return result;
+  }
+
+  // Extension (all trees of a forest): the forest's ferns packed into groups of <= 32 tests (gpc_hip_read_forest_groups).
+  // No implicit warm-up: call warmUp(groups).  A missing or malformed file: an empty vector (lastStatus() says why).
+  std::vector<FilterMask> readForestGroups(std::string path, int width, int height) {
+    std::vector<gpc_filter_mask> fm(GPC_MAX_GROUPS);
+    int n = 0;
+    const int st = gpc_hip_read_forest_groups(path.c_str(), width, height, fm.data(), (int)fm.size(), &n);
+    std::vector<FilterMask> groups;
+    if (st != GPC_OK) {
+      detail::fail(st, nullptr, "gpc_hip_read_forest_groups");
+      return groups;
+    }
+    for (int g = 0; g < n; ++g) {
+      std::vector<int32_t> mask(fm[g].mask, fm[g].mask + 2 * fm[g].num_tests);
+      std::vector<int> tau;
+      if (fm[g].type != 0) tau.assign(fm[g].tau, fm[g].tau + fm[g].num_tests);
+      groups.push_back(fm[g].type == 0 ? FilterMask(mask, width, height, 0) : FilterMask(mask, tau, width, height, 1));
+    }
+    return groups;
+  }
+
+  // Group mode overloads: every group matches as a forest of its own, the result is their union (group 0's records, then
+  // each later group's records not emitted before; include/gpc_hip.h, gpc_hip_set_forest_groups)
+  std::vector<ndb::Correspondence> stereoMatch(PreprocessedImage& simg, PreprocessedImage& timg, std::vector<FilterMask>& groups,
+                                               InferenceSettings settings) {
+    detail::ContextHolder& h = detail::holder();
+    if (!h.ctx || !upload(h, groups)) return std::vector<ndb::Correspondence>();
+    const gpc_settings s = settings.toC();
+    const int st = gpc_hip_stereo_match_begin(
+        h.ctx, simg.smooth.data(), simg.grad.data(), simg.mask.data(), (int)simg.mask.size(), timg.smooth.data(),
+        timg.grad.data(), timg.mask.data(), (int)timg.mask.size(), simg.smooth.cols(), simg.smooth.rows(), &s);
+    return fetchAll<ndb::Correspondence>(h, st, groups.size() * std::min(simg.mask.size(), timg.mask.size()), "gpc_hip_stereo_match");
+  }
+  std::vector<ndb::Support> rectifiedMatch(PreprocessedImage& simg, PreprocessedImage& timg, std::vector<FilterMask>& groups,
+                                           InferenceSettings settings) {
+    detail::ContextHolder& h = detail::holder();
+    if (!h.ctx || !upload(h, groups)) return std::vector<ndb::Support>();
+    const gpc_settings s = settings.toC();
+    const int st = gpc_hip_rectified_match_begin(
+        h.ctx, simg.smooth.data(), simg.grad.data(), simg.mask.data(), (int)simg.mask.size(), timg.smooth.data(),
+        timg.grad.data(), timg.mask.data(), (int)timg.mask.size(), simg.smooth.cols(), simg.smooth.rows(), &s);
+    return fetchAll<ndb::Support>(h, st, groups.size() * std::min(simg.mask.size(), timg.mask.size()), "gpc_hip_rectified_match");
+  }
+  std::vector<ndb::Support> matchPair(ndb::Buffer<uint8_t>& simg, ndb::Buffer<uint8_t>& timg, std::vector<FilterMask>& groups,
+                                      InferenceSettings settings, int* candidatesL = nullptr, int* candidatesR = nullptr) {
+    if (candidatesL) *candidatesL = 0;
+    if (candidatesR) *candidatesR = 0;
+    detail::ContextHolder& h = detail::holder();
+    if (!h.ctx || !upload(h, groups)) return std::vector<ndb::Support>();
+    const gpc_settings s = settings.toC();
+    const int st = gpc_hip_match_pair_begin(h.ctx, simg.data(), timg.data(), simg.cols(), simg.rows(), &s);
+    int cl = 0, cr = 0;
+    std::vector<ndb::Support> supp = fetchAll<ndb::Support>(h, st, (size_t)simg.rows() * simg.cols(), "gpc_hip_match_pair", &cl, &cr);
+    if (candidatesL) *candidatesL = cl;
+    if (candidatesR) *candidatesR = cr;
+    return supp;
+  }
+  // the warm-up of readForest for a group-mode forest (gpc_hip_warmup with the groups set)
+  void warmUp(std::vector<FilterMask>& groups) {
+    detail::ContextHolder& h = detail::holder(true);
+    if (!h.ctx || groups.empty()) return;
+    const std::vector<gpc_filter_mask> key = toC(groups);
+    if (same(h.warmed_groups, key)) return;
+    const int st0 = detail::last_status();
+    const std::string err0 = detail::last_error();
+    if (upload(h, groups) && gpc_hip_warmup(h.ctx, groups[0].width, groups[0].height, nullptr) == GPC_OK) h.warmed_groups = key;
+    detail::last_status() = st0;
+    detail::last_error() = err0;
   }
 
   // inference.hpp:302-333
@@ -395,7 +466,49 @@ class Forest {
     }
     h.uploaded = fm;
     h.have = true;
+    h.uploaded_groups.clear();
     return true;
+  }
+  static std::vector<gpc_filter_mask> toC(const std::vector<FilterMask>& groups) {
+    std::vector<gpc_filter_mask> fm(groups.size());
+    for (size_t g = 0; g < groups.size(); ++g) toC(groups[g], fm[g]);
+    return fm;
+  }
+  static bool same(const std::vector<gpc_filter_mask>& a, const std::vector<gpc_filter_mask>& b) {
+    return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), sizeof(gpc_filter_mask) * a.size()) == 0);
+  }
+  static bool upload(detail::ContextHolder& h, const std::vector<FilterMask>& groups) {
+    const std::vector<gpc_filter_mask> fm = toC(groups);
+    if (!h.uploaded_groups.empty() && same(h.uploaded_groups, fm)) return true;
+    const int st = fm.empty() ? GPC_E_INVALID : gpc_hip_set_forest_groups(h.ctx, fm.data(), (int)fm.size());
+    if (st != GPC_OK) {
+      detail::fail(st, h.ctx, "gpc_hip_set_forest_groups");
+      return false;
+    }
+    h.uploaded_groups = fm;
+    h.have = false;  // (the single-forest record no longer describes the context)
+    return true;
+  }
+  // begin + fetch of a group-mode call: the union can hold up to G * min(nL, nR) records; fetched again on GPC_E_CAPACITY
+  template <class T>
+  static std::vector<T> fetchAll(detail::ContextHolder& h, int st, size_t cap0, const char* what, int* cl = nullptr,
+                                 int* cr = nullptr) {
+    std::vector<T> out;
+    int n = 0;
+    if (st == GPC_OK) {
+      out.resize(cap0 + 1);
+      st = gpc_hip_match_fetch(h.ctx, out.data(), (int)out.size(), &n, cl, cr);
+      if (st == GPC_E_CAPACITY) {
+        out.resize((size_t)n);
+        st = gpc_hip_match_fetch(h.ctx, out.data(), (int)out.size(), &n, cl, cr);
+      }
+    }
+    if (st != GPC_OK) {
+      detail::fail(st, h.ctx, what);
+      return std::vector<T>();
+    }
+    out.resize((size_t)n);
+    return out;
   }
 };
 

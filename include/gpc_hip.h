@@ -127,6 +127,31 @@ int gpc_hip_parse_forest(const char* text, int width, int height, gpc_filter_mas
  * filter.hpp:547,619).  Offsets are decoded back to (dx,dy) with |d| <= 13. */
 int gpc_hip_set_forest(gpc_hip_ctx* ctx, const gpc_filter_mask* fm);
 
+/* ---- all trees of a forest (group mode) ------------------------------------------ */
+/* The forest's ferns, in file order, packed greedily into GROUPS of at most 32 tests: a group takes the next fern while
+ * its test count stays <= 32; a fern of more than 32 tests is cut into chunks of 32 (the remainder last), each a group of
+ * its own.  Group g equals what gpc_hip_read_forest returns for a file holding only group g's ferns (offsets for
+ * `width`, type 1 iff one of the group's own taus is nonzero, discarded = 0).  groups[0 .. *n_groups) are written;
+ * *n_groups is the true group count (GPC_E_CAPACITY if it exceeds cap).  More than GPC_MAX_GROUPS groups:
+ * GPC_E_UNSUPPORTED.  Truncated or garbage text: GPC_E_IO, as gpc_hip_parse_forest.  Host only. */
+#define GPC_MAX_GROUPS 32
+int gpc_hip_read_forest_groups(const char* path, int width, int height, gpc_filter_mask* groups, int cap, int* n_groups);
+int gpc_hip_parse_forest_groups(const char* text, int width, int height, gpc_filter_mask* groups, int cap, int* n_groups);
+/* Enters group mode (n_groups == 1 behaves exactly like gpc_hip_set_forest(ctx, groups)); gpc_hip_set_forest leaves it.
+ * Every group has the same width and height.  In group mode each group is matched as today's forest is (same arithmetic,
+ * settings and disparity filter), and gpc_hip_match_pair (+ _begin / gpc_hip_match_fetch), gpc_hip_rectified_match,
+ * gpc_hip_stereo_match (+ their _begin forms) and gpc_hip_match_batch_device return the UNION: group 0's records in
+ * today's order, then group 1's records not equal to one already emitted, and so on (supports compared by (x, y, d),
+ * correspondences by (src_x, src_y, tar_x, tar_y)).  A union holds up to n_groups * min(nL, nR) records: size outputs
+ * for that or fetch again on GPC_E_CAPACITY.  Candidate counts are unchanged.
+ * GPC_E_UNSUPPORTED in group mode: use_hashtable = 1, gpc_hip_match_batch, gpc_hip_match_batch_packed,
+ * gpc_hip_match_batch_device_packed, gpc_hip_hash_codes, two lanes (gpc_hip_set_pipeline(ctx, 2)). */
+int gpc_hip_set_forest_groups(gpc_hip_ctx* ctx, const gpc_filter_mask* groups, int n_groups);
+/* Dense code images of every group of the current forest, codes[n_groups][height][width]: plane g holds what
+ * gpc_hip_hash_codes gives for group g alone.  Outside group mode n_groups = 1 (the forest of gpc_hip_set_forest). */
+int gpc_hip_hash_codes_groups(gpc_hip_ctx* ctx, const uint8_t* smooth, const uint8_t* grad, int width, int height,
+                              uint32_t* codes);
+
 /* ---- host-buffer entry points (drop-in for the Forest methods) ---------------- */
 /* Forest::preprocessImage (inference.hpp:302-333): box + clearBoundary, sobel on the
  * raw image, ascending candidate indices with the 13-pixel margin.

@@ -17,6 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GPC_HIP_LIB") or os.path.join(HERE, "libgpc_hip.so")
 
 MAX_TESTS = 32
+MAX_GROUPS = 32   # GPC_MAX_GROUPS
 OK, E_INVALID, E_NO_DEVICE, E_HIP, E_CAPACITY, E_NO_FOREST, E_FOREST_RANGE, E_IO, E_UNSUPPORTED = range(9)
 
 SUPPORT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("d", "<f4")])
@@ -71,6 +72,7 @@ SYMBOLS = [
     "gpc_hip_abi_version", "gpc_hip_status_string", "gpc_hip_device_count", "gpc_hip_create",
     "gpc_hip_destroy", "gpc_hip_last_error", "gpc_hip_set_stream", "gpc_hip_synchronize",
     "gpc_hip_reserve", "gpc_hip_set_arithmetic", "gpc_hip_host_alloc", "gpc_hip_host_free", "gpc_hip_read_forest", "gpc_hip_parse_forest", "gpc_hip_set_forest",
+    "gpc_hip_read_forest_groups", "gpc_hip_parse_forest_groups", "gpc_hip_set_forest_groups", "gpc_hip_hash_codes_groups",
     "gpc_hip_warmup", "gpc_hip_preprocess", "gpc_hip_preprocess_begin", "gpc_hip_preprocess_fetch", "gpc_hip_resident_hits",
     "gpc_hip_rectified_match_begin", "gpc_hip_stereo_match_begin", "gpc_hip_match_pair_begin", "gpc_hip_match_fetch",
     "gpc_hip_hash_codes", "gpc_hip_rectified_match", "gpc_hip_stereo_match",
@@ -112,6 +114,10 @@ def load():
     L.gpc_hip_read_forest.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(FilterMask)]
     L.gpc_hip_parse_forest.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(FilterMask)]
     L.gpc_hip_set_forest.argtypes = [C.c_void_p, C.POINTER(FilterMask)]
+    L.gpc_hip_read_forest_groups.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(FilterMask), C.c_int, C.POINTER(C.c_int)]
+    L.gpc_hip_parse_forest_groups.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(FilterMask), C.c_int, C.POINTER(C.c_int)]
+    L.gpc_hip_set_forest_groups.argtypes = [C.c_void_p, C.POINTER(FilterMask), C.c_int]
+    L.gpc_hip_hash_codes_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.gpc_hip_preprocess.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.gpc_hip_warmup.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Settings)]
@@ -203,6 +209,23 @@ def parse_forest(text, width, height):
     fm = FilterMask()
     st = L.gpc_hip_parse_forest(text.encode(), width, height, C.byref(fm))
     return st, fm
+
+
+def _forest_groups(fn, arg, width, height):
+    L = load()
+    arr = (FilterMask * MAX_GROUPS)()
+    n = C.c_int(0)
+    st = fn(arg, width, height, arr, MAX_GROUPS, C.byref(n))
+    return st, [arr[i] for i in range(min(n.value, MAX_GROUPS))] if st == OK else []
+
+
+def read_forest_groups(path, width, height):
+    """The forest's ferns packed into groups of <= 32 tests (gpc_hip_read_forest_groups).  Returns (status, [FilterMask])."""
+    return _forest_groups(load().gpc_hip_read_forest_groups, os.fsencode(path), width, height)
+
+
+def parse_forest_groups(text, width, height):
+    return _forest_groups(load().gpc_hip_parse_forest_groups, text.encode(), width, height)
 
 
 # training (include/gpc_hip.h): gpc_split = the scoring fields of Feature::params; gpc_split_stats = splitStats
@@ -336,6 +359,28 @@ class Context:
 
     def set_forest(self, fm):
         self._ck(self.L.gpc_hip_set_forest(self.h, C.byref(fm)))
+        self._ngroups = 1
+
+    def set_forest_groups(self, groups):
+        """Group mode (gpc_hip_set_forest_groups): every group matches as a forest of its own, the results are their union."""
+        arr = (FilterMask * len(groups))(*groups)
+        self._ck(self.L.gpc_hip_set_forest_groups(self.h, arr, len(groups)))
+        self._ngroups = len(groups)
+
+    def load_forest_groups(self, path, width, height):
+        st, groups = read_forest_groups(path, width, height)
+        _check(self.L, None, st)
+        self.set_forest_groups(groups)
+        return groups
+
+    def hash_codes_groups(self, smooth, grad):
+        """Dense code images of every group of the current forest: (n_groups, H, W) uint32."""
+        smooth = np.ascontiguousarray(smooth, np.uint8)
+        grad = np.ascontiguousarray(grad, np.uint8)
+        H, W = smooth.shape
+        codes = np.empty((getattr(self, "_ngroups", 1), H, W), np.uint32)
+        self._ck(self.L.gpc_hip_hash_codes_groups(self.h, _ptr(smooth), _ptr(grad), W, H, _ptr(codes)))
+        return codes
 
     def load_forest(self, path, width, height):
         st, fm = read_forest(path, width, height)
@@ -385,7 +430,7 @@ class Context:
             fn = self.L.gpc_hip_rectified_match_begin if kind == "rectified" else self.L.gpc_hip_stereo_match_begin
             self._ck(fn(self.h, _ptr(sl), _ptr(gl), _ptr(ml), len(ml), _ptr(sr), _ptr(gr), _ptr(mr), len(mr), W, H, C.byref(s_)))
             dtype = SUPPORT_DTYPE if kind == "rectified" else CORR_DTYPE
-        cap = cap if cap is not None else W * H
+        cap = cap if cap is not None else W * H * getattr(self, "_ngroups", 1)
         out = np.empty(max(cap, 1), dtype)
         n, nl, nr = C.c_int(), C.c_int(-1), C.c_int(-1)
         st = self._ck(self.L.gpc_hip_match_fetch(self.h, _ptr(out), cap, C.byref(n), C.byref(nl), C.byref(nr)), allow=(E_CAPACITY,))
@@ -428,7 +473,7 @@ class Context:
         ml = np.ascontiguousarray(ml, np.int32)
         mr = np.ascontiguousarray(mr, np.int32)
         H, W = sl.shape
-        cap = cap if cap is not None else W * H
+        cap = cap if cap is not None else W * H * getattr(self, "_ngroups", 1)
         out = np.empty(max(cap, 1), dtype)
         n = C.c_int()
         st = fn(self.h, _ptr(sl), _ptr(gl), _ptr(ml), len(ml), _ptr(sr), _ptr(gr), _ptr(mr), len(mr), W, H,
@@ -448,7 +493,7 @@ class Context:
         rawL = np.ascontiguousarray(rawL, np.uint8)
         rawR = np.ascontiguousarray(rawR, np.uint8)
         H, W = rawL.shape
-        cap = cap if cap is not None else W * H
+        cap = cap if cap is not None else W * H * getattr(self, "_ngroups", 1)
         out = np.empty(max(cap, 1), SUPPORT_DTYPE)
         n, nl, nr = C.c_int(), C.c_int(), C.c_int()
         st = self.L.gpc_hip_match_pair(self.h, _ptr(rawL), _ptr(rawR), W, H, C.byref(settings), _ptr(out), cap,

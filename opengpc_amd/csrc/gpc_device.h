@@ -7,6 +7,9 @@
 #define GPC_R 13                    // patch radius == candidate margin (inference.hpp:322)
 #define GPC_NOCAND 0xFFFFFFFFu      // code-image value of a non-candidate pixel (valid codes have bit 31 clear)
 #define GPC_WAVE 64
+#ifndef GPC_MAX_GROUPS
+#define GPC_MAX_GROUPS 32          // groups of a forest in group mode (include/gpc_hip.h)
+#endif
 
 // per-image statistics block (int32 x 4): [0] candidates, [1] last row holding a candidate
 #define GPC_STAT_STRIDE 4

@@ -37,6 +37,7 @@
 #include "k_rowjoin_fused.h"
 #include "k_rows.h"
 #include "k_train.h"
+#include "k_union.h"
 
 namespace {
 
@@ -50,11 +51,12 @@ enum KernelId {
   KID_GLOBAL_SORT,
   KID_GLOBAL_MATCH,
   KID_TRAIN_EVAL,
+  KID_GROUP_UNION,
   KID_COUNT
 };
 const char* const kKernelNames[KID_COUNT] = {
     "k_preprocess", "k_hash", "k_row_join", "k_gather_rows",
-    "k_mask", "k_global_keys", "k_global_sort", "k_global_match", "k_train_eval"};
+    "k_mask", "k_global_keys", "k_global_sort", "k_global_match", "k_train_eval", "k_group_union"};
 
 struct DevBuf {
   void* p = nullptr;
@@ -224,6 +226,13 @@ struct gpc_hip_ctx {
   GpcForestDev forest_naive;  // tests reversed: slot u = test T-1-u lands on bit u (MSB-first codes), raw int tau
   int forest_w = 0, forest_h = 0;
   gpc_filter_mask forest_src;  // what gpc_hip_set_forest was last given: the same forest again costs nothing
+  // group mode (gpc_hip_set_forest_groups with more than one group; gpc_hip_set_forest leaves it): the hash kernel runs
+  // every group's tests (k_hash_groups), the joins run over virtual pairs p * ngroups + g, k_group_union unites them
+  int ngroups = 0;             // 0 outside group mode
+  int gmax_tests = 0;          // the largest group (code_bits, wide_codes)
+  bool gtau = false;           // one of the groups has a nonzero tau
+  DevBuf gforest_dev;          // [3][GPC_MAX_GROUPS] GpcForestDev: SSE order, Naive order, SSE with the tall tile's offsets
+  DevBuf vstats, vcand, vout, vcnt, vncand, uplane, ublk, gdense;  // virtual-pair statistics / candidates / results, union state
 
   // workspaces
   DevBuf raw, smooth, grad, candmap, codes, staged, rowcnt, stats, out, counts, ncand, mask;
@@ -313,6 +322,7 @@ struct gpc_hip_ctx {
   // caller's page-locked array), the count and the candidate counts in h_cnt[0 .. 2]
   struct PendingMatch {
     bool active = false, direct = false, have_ncand = false;
+    void* dev_out = nullptr;  // group mode: the union's records are in device memory (c->gdense), cap_dev of them at most
     bool packed = false;   // the arena holds [H row counts | cap_dev words xL | xR << 16] (epipolar sort-matcher): 4 bytes
                            // per support over the link instead of 12, expanded into the caller's array by the workers
     size_t esz = 0;
@@ -715,8 +725,10 @@ int run_preprocess(gpc_hip_ctx* c, const uint8_t* d_raw0, const uint8_t* d_raw1,
 }
 
 // smooth/grad/(candmap) device pointers for nimg images -> code image
+// groups > 0: k_hash_groups over the context's groups (gpc_hip_set_forest_groups), image 2p + s writing group g as image
+// (p * groups + g) * 2 + s (gstep 2) or, one image, g (gstep 1); the statistics of those virtual images in c->stats
 int run_hash(gpc_hip_ctx* c, const uint8_t* d_smooth, const uint8_t* d_grad, const uint8_t* d_cand,
-             int W, int H, int nimg, bool dense, uint32_t* d_codes) {
+             int W, int H, int nimg, bool dense, uint32_t* d_codes, int groups = 0, int gstep = 2) {
   if (!c->have_forest) return GPC_E_NO_FOREST;
   // tiles per workgroup: each CU holds 2 workgroups (67 KiB of LDS each); walking several
   // vertically adjacent tiles hides the next window's load latency, but the grid must still fill
@@ -775,8 +787,36 @@ int run_hash(gpc_hip_ctx* c, const uint8_t* d_smooth, const uint8_t* d_grad, con
   const long nwg_all = (long)grid.x * grid.y * grid.z;
   const int last_from = nwg_all > slots ? (int)(nwg_all - slots) : 0;
   Timed t(c, KID_HASH);
-  const bool tau = c->forest.type != 0;
+  const bool tau = groups > 0 ? c->gtau : c->forest.type != 0;
   int32_t* st = (int32_t*)c->stats.p;
+  if (groups > 0) {
+    const GpcForestDev* gf = (const GpcForestDev*)c->gforest_dev.p;
+    snprintf(c->launch_name[KID_HASH], sizeof c->launch_name[0], "gpc::k_hash_groups<%s, %s, %s, %s, %d>", tau ? "true" : "false",
+             dense ? "true" : "false", c->naive ? "true" : "false", gbits ? "true" : "false", ty);
+#define LAUNCH_HASH_G(TAU, DENSE, NAIVE, GB, TY, FD)                                                                       \
+  hipLaunchKernelGGL((gpc::k_hash_groups<TAU, DENSE, NAIVE, GB, TY>), grid, dim3(HT_THREADS), 0, c->stream, d_smooth, d_grad, \
+                     d_cand, d_codes, W, H, gf + (FD) * GPC_MAX_GROUPS, st, tpw, last_from, groups, gstep)
+    if (gbits) {
+      if (ty == HT_Y_TALL) {
+        if (tau) LAUNCH_HASH_G(true, false, false, true, HT_Y_TALL, 2); else LAUNCH_HASH_G(false, false, false, true, HT_Y_TALL, 2);
+      } else {
+        if (tau) LAUNCH_HASH_G(true, false, false, true, HT_Y, 0); else LAUNCH_HASH_G(false, false, false, true, HT_Y, 0);
+      }
+    } else if (c->naive) {
+      if (tau && dense) LAUNCH_HASH_G(true, true, true, false, HT_Y, 1);
+      else if (tau) LAUNCH_HASH_G(true, false, true, false, HT_Y, 1);
+      else if (dense) LAUNCH_HASH_G(false, true, true, false, HT_Y, 1);
+      else LAUNCH_HASH_G(false, false, true, false, HT_Y, 1);
+    } else {
+      if (tau && dense) LAUNCH_HASH_G(true, true, false, false, HT_Y, 0);
+      else if (tau) LAUNCH_HASH_G(true, false, false, false, HT_Y, 0);
+      else if (dense) LAUNCH_HASH_G(false, true, false, false, HT_Y, 0);
+      else LAUNCH_HASH_G(false, false, false, false, HT_Y, 0);
+    }
+#undef LAUNCH_HASH_G
+    HIPCHK(c, hipGetLastError());
+    return GPC_OK;
+  }
   snprintf(c->launch_name[KID_HASH], sizeof c->launch_name[0], "gpc::k_hash<%s, %s, %s, %s, %d>", tau ? "true" : "false",
            dense ? "true" : "false", c->naive ? "true" : "false", gbits ? "true" : "false", ty);
 #define LAUNCH_HASH(TAU, DENSE, NAIVE)                                                                    \
@@ -811,14 +851,15 @@ int run_hash(gpc_hip_ctx* c, const uint8_t* d_smooth, const uint8_t* d_grad, con
 // Significant bits of the codes the current forest can produce (the partitioned matcher bins on the top ones of
 // these, k_partition.h).  SSE placement (filter.hpp:574-595): test t -> bit t for
 // t <= 7, test 8 is OR-ed into bit 0, test t -> bit t-1 for t >= 9; Naive (filter.hpp:245-249): T bits.
+// (group mode: the largest group's -- one planner width for every group; a smaller group's codes then fill the low bins)
 int code_bits(const gpc_hip_ctx* c) {
-  const int T = c->forest.num_tests;
+  const int T = c->ngroups > 1 ? c->gmax_tests : c->forest.num_tests;
   if (c->naive) return T;
   return T <= 8 ? T : T - 1;
 }
 
 // SSE=OFF arithmetic with 32 tests: codes use bit 31 and 0xFFFFFFFF is a code (k_rowjoin.h, WIDE)
-bool wide_codes(const gpc_hip_ctx* c) { return c->naive && c->forest.num_tests == 32; }
+bool wide_codes(const gpc_hip_ctx* c) { return c->naive && (c->ngroups > 1 ? c->gmax_tests : c->forest.num_tests) == 32; }
 
 // How the join kernel covers a row of W pixels: NT threads x SPT pixel slots, table of 1 << log2s slots.
 struct JoinPlan {
@@ -1826,6 +1867,72 @@ __global__ void k_stats_init(int32_t* __restrict__ stats, int nimg) {
 
 namespace {
 
+// Group mode: hash + match + union of npairs pairs whose smoothed images (and gradient / candidate images) are on the device.
+// d_cand_hash: the candidate map k_hash reads (null: the gradient image's); d_cand: the candidate bytes of the matchers.
+// The groups' codes go to c->codes as virtual pairs [pair][group][side][H][W] with statistics of their own (vstats); the
+// joins run unchanged over the npairs * G virtual pairs into vout (a group has at most one record per left pixel: the
+// image's candidate count bounds it), and k_group_union writes each pair's union to d_out[p][cap] (true totals into
+// d_counts, candidate counts into d_ncand).
+int run_group_match(gpc_hip_ctx* c, const uint8_t* d_sm, const uint8_t* d_gr, const uint8_t* d_cand_hash, int W, int H,
+                    int npairs, const gpc_settings* s, int mode, const uint8_t* d_cand, void* d_out, long cap,
+                    int32_t* d_counts, int32_t* d_ncand) {
+  if (s->use_hashtable) return GPC_E_UNSUPPORTED;  // (its pair / triplet rules may emit a left pixel twice)
+  const int G = c->ngroups;
+  const size_t n = (size_t)W * H;
+  const int npv = npairs * G;
+  const size_t esz = mode == 0 ? sizeof(gpc_support) : sizeof(gpc_correspondence);
+  const long vcap = (long)(W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;
+  CHK(ensure(c, c->codes, sizeof(uint32_t) * n * 2 * npv));
+  CHK(ensure(c, c->vstats, sizeof(int32_t) * GPC_STAT_STRIDE * 2 * npv));
+  CHK(ensure(c, c->vout, esz * (size_t)vcap * npv));
+  CHK(ensure(c, c->vcnt, sizeof(int32_t) * npv));
+  CHK(ensure(c, c->vncand, sizeof(int32_t) * 2 * npv));
+  hipLaunchKernelGGL(gpc::k_stats_init, dim3((2 * npv + 63) / 64), dim3(64), 0, c->stream, (int32_t*)c->vstats.p, 2 * npv);
+  // (the virtual images' statistics stand in for the real ones while the groups are hashed and joined)
+  std::swap(c->stats, c->vstats);
+  int st = run_hash(c, d_sm, d_gr, d_cand_hash, W, H, 2 * npairs, false, (uint32_t*)c->codes.p, G, 2);
+  const uint8_t* vc = d_cand;
+  if (st == GPC_OK && wide_codes(c) && d_cand) {
+    // the WIDE joins read the candidate bytes of their (virtual) image: one copy per group
+    st = ensure(c, c->vcand, 2 * n * npv);
+    for (int p = 0; p < npairs && st == GPC_OK; ++p)
+      for (int g = 0; g < G && st == GPC_OK; ++g)
+        if (hipMemcpyAsync((uint8_t*)c->vcand.p + (size_t)(p * G + g) * 2 * n, d_cand + (size_t)p * 2 * n, 2 * n,
+                           hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+          st = GPC_E_HIP;
+    vc = (const uint8_t*)c->vcand.p;
+  }
+  if (st == GPC_OK)
+    st = run_match(c, W, H, npv, s, mode, vc, c->vout.p, (int)vcap, (int32_t*)c->vcnt.p, (int32_t*)c->vncand.p);
+  std::swap(c->stats, c->vstats);
+  CHK(st);
+  const int nchunk = (int)((vcap + UN_CHUNK - 1) / UN_CHUNK);
+  CHK(ensure(c, c->uplane, sizeof(uint32_t) * n * npv));
+  CHK(ensure(c, c->ublk, sizeof(int32_t) * (size_t)nchunk * npv));
+  Timed t(c, KID_GROUP_UNION);
+  snprintf(c->launch_name[KID_GROUP_UNION], sizeof c->launch_name[0], "gpc::k_group_union<%s>", mode == 0 ? "false" : "true");
+  HIPCHK(c, hipMemsetAsync(c->uplane.p, 0xFF, sizeof(uint32_t) * n * npv, c->stream));
+  const dim3 sgrid(nchunk < 512 ? nchunk : 512, npv), cgrid(nchunk, npv);
+#define UNION_LAUNCH(CORR)                                                                                                  \
+  do {                                                                                                                     \
+    typedef gpc::UnRec<CORR> R_;                                                                                           \
+    const R_* vo_ = (const R_*)c->vout.p;                                                                                  \
+    hipLaunchKernelGGL((gpc::k_group_union_scatter<CORR>), sgrid, dim3(UN_THREADS), 0, c->stream, vo_,                     \
+                       (const int32_t*)c->vcnt.p, vcap, W, H, (uint32_t*)c->uplane.p, G);                                  \
+    hipLaunchKernelGGL((gpc::k_group_union_count<CORR>), cgrid, dim3(UN_THREADS), 0, c->stream, vo_,                       \
+                       (const int32_t*)c->vcnt.p, vcap, W, H, (const uint32_t*)c->uplane.p, G, (int32_t*)c->ublk.p, nchunk); \
+    hipLaunchKernelGGL(gpc::k_group_union_scan, dim3(npairs), dim3(1024), 0, c->stream, (int32_t*)c->ublk.p, nchunk, G,    \
+                       d_counts, d_ncand, (const int32_t*)c->vstats.p);                                                    \
+    hipLaunchKernelGGL((gpc::k_group_union<CORR>), cgrid, dim3(UN_THREADS), 0, c->stream, vo_, (const int32_t*)c->vcnt.p,  \
+                       vcap, W, H, (const uint32_t*)c->uplane.p, G, (const int32_t*)c->ublk.p, nchunk, (R_*)d_out, cap);   \
+  } while (0)
+  if (mode == 0) UNION_LAUNCH(false);
+  else UNION_LAUNCH(true);
+#undef UNION_LAUNCH
+  HIPCHK(c, hipGetLastError());
+  return GPC_OK;
+}
+
 }  // namespace
 
 // =================================================================== C ABI
@@ -2039,10 +2146,17 @@ int gpc_hip_reserve(gpc_hip_ctx* c, int W, int H, int max_pairs) {
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)W * H;
   const int nimg = 2 * max_pairs;
+  const int G = c->ngroups > 1 ? c->ngroups : 1;  // group mode: codes and statistics per group (virtual pairs)
   CHK(ensure(c, c->raw, n * nimg));
   CHK(ensure(c, c->smooth, n * nimg));
   CHK(ensure(c, c->grad, n * nimg));
-  CHK(ensure(c, c->codes, sizeof(uint32_t) * n * nimg));
+  CHK(ensure(c, c->codes, sizeof(uint32_t) * n * nimg * G));
+  if (G > 1) {
+    CHK(ensure(c, c->vstats, sizeof(int32_t) * GPC_STAT_STRIDE * nimg * G));
+    CHK(ensure(c, c->vcnt, sizeof(int32_t) * max_pairs * G));
+    CHK(ensure(c, c->vncand, sizeof(int32_t) * nimg * G));
+    CHK(ensure(c, c->uplane, sizeof(uint32_t) * n * max_pairs * G));
+  }
   CHK(ensure(c, c->staged, sizeof(uint32_t) * n * max_pairs));
   CHK(ensure(c, c->rowcnt, sizeof(int32_t) * (size_t)H * nimg));
   CHK(ensure(c, c->stats, sizeof(int32_t) * GPC_STAT_STRIDE * nimg));
@@ -2121,19 +2235,13 @@ int gpc_hip_read_forest(const char* path, int W, int H, gpc_filter_mask* fm) {
   return gpc_hip_parse_forest(text.c_str(), W, H, fm);
 }
 
-int gpc_hip_set_forest(gpc_hip_ctx* c, const gpc_filter_mask* fm) {
-  if (!c || !fm) return GPC_E_INVALID;
-  if (fm->num_tests < 0 || fm->num_tests > GPC_MAX_TESTS) return GPC_E_INVALID;
-  CHK(check_dims(fm->width, fm->height));
-  // The header-only C++ API is stateless like the reference's Forest and hands the forest over with every match call:
-  // the same tests again must not cost a stream synchronisation and a blocking copy (~30 us of a 0.2 ms call)
-  if (c->have_forest && fm->num_tests == c->forest_src.num_tests && fm->type == c->forest_src.type &&
-      fm->width == c->forest_src.width && fm->height == c->forest_src.height &&
-      memcmp(fm->mask, c->forest_src.mask, sizeof(int32_t) * 2 * (size_t)fm->num_tests) == 0 &&
-      memcmp(fm->tau, c->forest_src.tau, sizeof(int32_t) * (size_t)fm->num_tests) == 0)
-    return GPC_OK;
+}  // extern "C"
+
+namespace {
+// The hash kernel's form of a forest: f in SSE order; fn reversed for the Naive arithmetic; ft SSE order with the tall
+// tile's LDS offsets
+int forest_dev_of(const gpc_filter_mask* fm, GpcForestDev& f, GpcForestDev& fn, GpcForestDev& ft) {
   const int W = fm->width;
-  GpcForestDev f, fn, ft;  // SSE order; reversed for the Naive arithmetic; SSE order with the tall tile's LDS offsets
   memset(&f, 0, sizeof f);
   memset(&fn, 0, sizeof fn);
   memset(&ft, 0, sizeof ft);
@@ -2178,6 +2286,26 @@ int gpc_hip_set_forest(gpc_hip_ctx* c, const gpc_filter_mask* fm) {
   }
   f.num_tests = fn.num_tests = ft.num_tests = fm->num_tests;
   f.type = fn.type = ft.type = fm->type ? 1 : 0;
+  return GPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gpc_hip_set_forest(gpc_hip_ctx* c, const gpc_filter_mask* fm) {
+  if (!c || !fm) return GPC_E_INVALID;
+  if (fm->num_tests < 0 || fm->num_tests > GPC_MAX_TESTS) return GPC_E_INVALID;
+  CHK(check_dims(fm->width, fm->height));
+  // The header-only C++ API is stateless like the reference's Forest and hands the forest over with every match call:
+  // the same tests again must not cost a stream synchronisation and a blocking copy (~30 us of a 0.2 ms call)
+  // (group mode leaves forest_src invalid: the same forest as before group mode is set again)
+  if (c->have_forest && fm->num_tests == c->forest_src.num_tests && fm->type == c->forest_src.type &&
+      fm->width == c->forest_src.width && fm->height == c->forest_src.height &&
+      memcmp(fm->mask, c->forest_src.mask, sizeof(int32_t) * 2 * (size_t)fm->num_tests) == 0 &&
+      memcmp(fm->tau, c->forest_src.tau, sizeof(int32_t) * (size_t)fm->num_tests) == 0)
+    return GPC_OK;
+  GpcForestDev f, fn, ft;
+  CHK(forest_dev_of(fm, f, fn, ft));
   c->forest = f;
   c->forest_naive = fn;
   HIPCHK(c, hipSetDevice(c->device));
@@ -2189,6 +2317,114 @@ int gpc_hip_set_forest(gpc_hip_ctx* c, const gpc_filter_mask* fm) {
   c->forest_w = fm->width;
   c->forest_h = fm->height;
   c->forest_src = *fm;
+  c->have_forest = true;
+  c->ngroups = 0;
+  return GPC_OK;
+}
+
+int gpc_hip_parse_forest_groups(const char* text, int W, int H, gpc_filter_mask* groups, int cap, int* n_groups) {
+  if (!text || !n_groups || cap < 0 || (cap > 0 && !groups)) return GPC_E_INVALID;
+  *n_groups = 0;
+  // the whole text first (a truncated file yields GPC_E_IO and no groups, as gpc_hip_parse_forest)
+  struct Test { int ix, iy, jx, jy, tau; };
+  std::vector<std::vector<Test>> ferns;
+  const char* p = text;
+  int num_ferns = 0;
+  if (!next_int(p, num_ferns)) return GPC_E_IO;
+  for (int i = 0; i < num_ferns; ++i) {
+    int fern_id, num_tests;
+    std::string scale;
+    if (!next_int(p, fern_id) || !next_tok(p, scale) || !next_int(p, num_tests)) return GPC_E_IO;
+    ferns.emplace_back();
+    for (int j = 0; j < num_tests; ++j) {
+      int level;
+      Test t;
+      if (!next_int(p, level) || !next_int(p, t.ix) || !next_int(p, t.iy) || !next_int(p, t.jx) || !next_int(p, t.jy) ||
+          !next_int(p, t.tau))
+        return GPC_E_IO;
+      ferns.back().push_back(t);
+    }
+  }
+  // greedy packing: a group takes the next fern while it stays <= 32 tests; a longer fern is cut into chunks of 32 (the
+  // remainder last), each a group of its own
+  std::vector<std::vector<Test>> packed;
+  bool open = false;  // the last group may take more ferns
+  for (const auto& f : ferns) {
+    if ((int)f.size() > GPC_MAX_TESTS) {
+      for (size_t k = 0; k < f.size(); k += GPC_MAX_TESTS)
+        packed.emplace_back(f.begin() + k, f.begin() + std::min(f.size(), k + GPC_MAX_TESTS));
+      open = false;
+    } else if (open && packed.back().size() + f.size() <= GPC_MAX_TESTS) {
+      packed.back().insert(packed.back().end(), f.begin(), f.end());
+    } else if (!f.empty() || !open) {
+      packed.push_back(f);
+      open = true;
+    }
+  }
+  if (packed.empty()) packed.emplace_back();  // (no tests at all: the empty forest gpc_hip_parse_forest gives)
+  const int ng = (int)packed.size();
+  *n_groups = ng;
+  if (ng > GPC_MAX_GROUPS) return GPC_E_UNSUPPORTED;
+  for (int g = 0; g < ng && g < cap; ++g) {
+    gpc_filter_mask* fm = &groups[g];
+    memset(fm, 0, sizeof(*fm));
+    fm->width = W;
+    fm->height = H;
+    int nonzero = 0;
+    for (const Test& t : packed[(size_t)g]) {
+      const int k = fm->num_tests++;
+      fm->mask[2 * k] = (int32_t)((uint32_t)t.ix + (uint32_t)t.iy * (uint32_t)W);   // (as gpc_hip_parse_forest)
+      fm->mask[2 * k + 1] = (int32_t)((uint32_t)t.jx + (uint32_t)t.jy * (uint32_t)W);
+      fm->tau[k] = t.tau;
+      if (t.tau != 0) nonzero++;
+    }
+    fm->type = nonzero ? 1 : 0;
+  }
+  return ng > cap ? GPC_E_CAPACITY : GPC_OK;
+}
+
+int gpc_hip_read_forest_groups(const char* path, int W, int H, gpc_filter_mask* groups, int cap, int* n_groups) {
+  if (!path || !n_groups || cap < 0 || (cap > 0 && !groups)) return GPC_E_INVALID;
+  *n_groups = 0;
+  FILE* fp = fopen(path, "rb");
+  if (!fp) return GPC_E_IO;
+  std::string text;
+  char buf[4096];
+  size_t got;
+  while ((got = fread(buf, 1, sizeof buf, fp)) > 0) text.append(buf, got);
+  fclose(fp);
+  return gpc_hip_parse_forest_groups(text.c_str(), W, H, groups, cap, n_groups);
+}
+
+int gpc_hip_set_forest_groups(gpc_hip_ctx* c, const gpc_filter_mask* groups, int n_groups) {
+  if (!c || !groups || n_groups < 1 || n_groups > GPC_MAX_GROUPS) return GPC_E_INVALID;
+  if (n_groups == 1) return gpc_hip_set_forest(c, groups);
+  if (c->pipeline > 1) return GPC_E_UNSUPPORTED;
+  std::vector<GpcForestDev> dev((size_t)3 * GPC_MAX_GROUPS);
+  int maxt = 0;
+  bool tau = false;
+  for (int g = 0; g < n_groups; ++g) {
+    const gpc_filter_mask* fm = &groups[g];
+    if (fm->num_tests < 0 || fm->num_tests > GPC_MAX_TESTS) return GPC_E_INVALID;
+    if (fm->width != groups[0].width || fm->height != groups[0].height) return GPC_E_INVALID;
+    CHK(check_dims(fm->width, fm->height));
+    CHK(forest_dev_of(fm, dev[(size_t)g], dev[(size_t)GPC_MAX_GROUPS + g], dev[(size_t)2 * GPC_MAX_GROUPS + g]));
+    maxt = std::max(maxt, fm->num_tests);
+    tau = tau || fm->type != 0;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  CHK(ensure(c, c->gforest_dev, sizeof(GpcForestDev) * dev.size()));
+  CHK(drain_lanes(c));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // a launch in flight may still read the previous tests
+  HIPCHK(c, hipMemcpy(c->gforest_dev.p, dev.data(), sizeof(GpcForestDev) * dev.size(), hipMemcpyHostToDevice));
+  c->forest = dev[0];
+  c->forest_naive = dev[(size_t)GPC_MAX_GROUPS];
+  c->forest_w = groups[0].width;
+  c->forest_h = groups[0].height;
+  c->forest_src.num_tests = -1;  // (no forest of gpc_hip_set_forest is current)
+  c->gmax_tests = maxt;
+  c->gtau = tau;
+  c->ngroups = n_groups;
   c->have_forest = true;
   return GPC_OK;
 }
@@ -2338,6 +2574,7 @@ int gpc_hip_resident_hits(const gpc_hip_ctx* c) { return c ? c->resident_hits : 
 int gpc_hip_hash_codes(gpc_hip_ctx* c, const uint8_t* smooth, const uint8_t* grad, int W, int H,
                        uint32_t* codes) {
   if (!c || !smooth || !grad || !codes) return GPC_E_INVALID;
+  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;  // (gpc_hip_hash_codes_groups)
   CHK(check_dims(W, H));
   CHK(forest_matches(c, W, H));
   HIPCHK(c, hipSetDevice(c->device));
@@ -2363,6 +2600,35 @@ int gpc_hip_hash_codes(gpc_hip_ctx* c, const uint8_t* smooth, const uint8_t* gra
   CHK(dev_copy16(c, d_arena, c->codes.p, sizeof(uint32_t) * n));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   host_copy(c, codes, c->h_xfer, sizeof(uint32_t) * n, true);
+  host_copy_wait(c);
+  return GPC_OK;
+}
+
+int gpc_hip_hash_codes_groups(gpc_hip_ctx* c, const uint8_t* smooth, const uint8_t* grad, int W, int H, uint32_t* codes) {
+  if (!c || !smooth || !grad || !codes) return GPC_E_INVALID;
+  CHK(check_dims(W, H));
+  CHK(forest_matches(c, W, H));
+  HIPCHK(c, hipSetDevice(c->device));
+  const int G = c->ngroups > 1 ? c->ngroups : 1;
+  const size_t n = (size_t)W * H;
+  CHK(ensure(c, c->smooth, n));
+  CHK(ensure(c, c->grad, n));
+  CHK(ensure(c, c->gdense, sizeof(uint32_t) * n * G));
+  uint8_t* d_arena = nullptr;
+  CHK(xfer_reserve(c, sizeof(uint32_t) * n * G, &d_arena));
+  CHK(ensure_pool(c));
+  host_copy(c, c->h_xfer, smooth, n, true);
+  host_copy(c, c->h_xfer + n, grad, n, true);
+  host_copy_wait(c);
+  CHK(dev_copy16(c, c->smooth.p, d_arena, n));
+  c->grad_is_bits = false;
+  CHK(dev_copy16(c, c->grad.p, d_arena + n, n));
+  HIPCHK(c, hipMemsetAsync(c->gdense.p, 0, sizeof(uint32_t) * n * G, c->stream));  // (the reference's zero-filled buffer)
+  CHK(run_hash(c, (const uint8_t*)c->smooth.p, (const uint8_t*)c->grad.p, nullptr, W, H, 1, true, (uint32_t*)c->gdense.p,
+               G > 1 ? G : 0, 1));
+  CHK(dev_copy16(c, d_arena, c->gdense.p, sizeof(uint32_t) * n * G));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  host_copy(c, codes, c->h_xfer, sizeof(uint32_t) * n * G, true);
   host_copy_wait(c);
   return GPC_OK;
 }
@@ -2394,10 +2660,17 @@ static int match_preprocessed_begin(gpc_hip_ctx* c, const uint8_t* smoothL, cons
   // Supports of the epipolar sort-matcher cross the link PACKED (x | xR << 16 + the row counts: 4 bytes instead of 12 -- a
   // 1024x436 pair's 3.2 MB of records were 60 us of the link, a third of the call) and are expanded into the caller's
   // array by the worker threads, who read 1.1 MB where they copied 3.2
-  const bool packed = mode == 0 && !direct_out && s->epipolar_mode && !s->use_hashtable && !c->no_pair_packed;
+  // (group mode: the union stays on the device until match_fetch knows its size)
+  const bool groups = c->ngroups > 1;
+  if (groups) {
+    if (s->use_hashtable) return GPC_E_UNSUPPORTED;
+    direct_out = nullptr;
+  }
+  const bool packed = mode == 0 && !direct_out && s->epipolar_mode && !s->use_hashtable && !c->no_pair_packed && !groups;
   const size_t rows_bytes = pad16(sizeof(int32_t) * (size_t)H);
-  const size_t out_bytes = packed ? rows_bytes + pad16(sizeof(uint32_t) * (size_t)(cap_dev > 0 ? cap_dev : 1))
-                                  : pad16(esz * (size_t)(cap_dev > 0 ? cap_dev : 1));
+  const size_t out_bytes = groups ? 0
+                           : packed ? rows_bytes + pad16(sizeof(uint32_t) * (size_t)(cap_dev > 0 ? cap_dev : 1))
+                                    : pad16(esz * (size_t)(cap_dev > 0 ? cap_dev : 1));
   const int sl = resident_slot(c, smoothL, gradL, maskL, nL, W, H);
   const int sr = sl >= 0 ? resident_slot(c, smoothR, gradR, maskR, nR, W, H) : -1;
   const bool resident = sl >= 0 && sr >= 0;
@@ -2405,7 +2678,8 @@ static int match_preprocessed_begin(gpc_hip_ctx* c, const uint8_t* smoothL, cons
   const size_t mL = pad16(sizeof(int32_t) * (size_t)nL), mR = pad16(sizeof(int32_t) * (size_t)nR);
   uint8_t* d_arena = nullptr;
   const size_t in_bytes = resident ? 0 : 4 * n + mL + mR;
-  if (!direct_out || in_bytes) CHK(xfer_reserve(c, (direct_out ? 0 : out_bytes) + in_bytes, &d_arena));
+  // (group mode from resident images: nothing crosses the link before match_fetch)
+  if ((!direct_out && out_bytes) || in_bytes) CHK(xfer_reserve(c, (direct_out ? 0 : out_bytes) + in_bytes, &d_arena));
   const size_t in_off = direct_out ? 0 : out_bytes;
   void* d_out = direct_out ? direct_out : d_arena;
   const uint8_t* d_sm = nullptr;
@@ -2462,6 +2736,15 @@ static int match_preprocessed_begin(gpc_hip_ctx* c, const uint8_t* smoothL, cons
     d_cand = d_cm;
   }
   c->grad_is_bits = false;  // byte images
+  c->pend.dev_out = nullptr;
+  if (groups) {
+    const long cap_u = (long)c->ngroups * ((long)(W - 2 * GPC_R) * (H - 2 * GPC_R)) + 1;
+    CHK(ensure(c, c->gdense, esz * (size_t)cap_u));
+    CHK(run_group_match(c, d_sm, d_gr, resident ? nullptr : d_cand, W, H, 1, s, mode, d_cand, c->gdense.p, cap_u, d_cnt,
+                        nullptr));
+    cap_dev = (int)std::min(cap_u, (long)INT32_MAX);
+    c->pend.dev_out = c->gdense.p;
+  } else {
   hipLaunchKernelGGL(gpc::k_stats_init, dim3(1), dim3(64), 0, c->stream, (int32_t*)c->stats.p, 2);
   CHK(run_hash(c, d_sm, d_gr, resident ? nullptr : d_cand, W, H, 2, false, (uint32_t*)c->codes.p));
   if (packed) {
@@ -2469,6 +2752,7 @@ static int match_preprocessed_begin(gpc_hip_ctx* c, const uint8_t* smoothL, cons
     CHK(run_match(c, W, H, 1, s, 2, d_cand, d_arena + rows_bytes, cap_dev, d_cnt, nullptr, &po));
   } else {
     CHK(run_match(c, W, H, 1, s, mode, d_cand, d_out, cap_dev, d_cnt, nullptr));
+  }
   }
   c->pend.active = true;
   c->pend.direct = direct_out != nullptr;
@@ -2494,7 +2778,18 @@ static int match_fetch(gpc_hip_ctx* c, void* out, int cap, int* n_out, int* ncl,
   }
   int ncopy = cnt < cap ? cnt : cap;
   if (ncopy > c->pend.cap_dev) ncopy = c->pend.cap_dev;
-  if (c->pend.packed && ncopy > 0) {
+  if (c->pend.dev_out && ncopy > 0) {
+    // group mode: the first ncopy records of the union into the arena, then into the caller's array
+    const size_t bytes = c->pend.esz * (size_t)ncopy;
+    uint8_t* d_arena = nullptr;
+    CHK(xfer_reserve(c, bytes, &d_arena));
+    HIPCHK(c, hipMemcpyAsync(c->h_xfer, c->pend.dev_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const bool par = bytes >= 256 * 1024;
+    if (par) CHK(ensure_pool(c));
+    host_copy(c, out, c->h_xfer, bytes, par);
+    if (par) host_copy_wait(c);
+  } else if (c->pend.packed && ncopy > 0) {
     const int H = c->pend.H;
     const int32_t* rows = reinterpret_cast<const int32_t*>(c->h_xfer);
     const uint32_t* words = reinterpret_cast<const uint32_t*>(c->h_xfer + pad16(sizeof(int32_t) * (size_t)H));
@@ -2577,6 +2872,12 @@ int gpc_hip_match_batch_device(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint
   CHK(forest_matches(c, W, H));
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)W * H;
+  if (c->ngroups > 1) {
+    if (c->pipeline > 1 || s->use_hashtable) return GPC_E_UNSUPPORTED;
+    CHK(run_preprocess(c, d_rawL, d_rawR, W, H, npairs, 2, s->gradient_threshold, true));
+    return run_group_match(c, (const uint8_t*)c->smooth.p, (const uint8_t*)c->grad.p, nullptr, W, H, npairs, s, 0,
+                           (const uint8_t*)c->grad.p, d_out, cap_per_pair, d_counts, d_ncand);
+  }
   if (c->pipeline > 1 && s->epipolar_mode && !s->use_hashtable) {
     // Two lanes: this call goes to the lane the previous one did not take.  Its inputs are what the context's stream has
     // produced so far (e_in); its k_preprocess starts when the other lane's k_hash is done -- beside that lane's join --
@@ -2616,6 +2917,7 @@ int gpc_hip_match_batch_device(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint
 // Experiment hook, not part of the C ABI (include/gpc_hip.h does not declare it): see gpc_hip_ctx::dbg_wait_pre.
 int gpc_hip_set_pipeline(gpc_hip_ctx* c, int lanes) {
   if (!c || (lanes != 1 && lanes != 2)) return GPC_E_INVALID;
+  if (lanes == 2 && c->ngroups > 1) return GPC_E_UNSUPPORTED;
   HIPCHK(c, hipSetDevice(c->device));
   CHK(drain_lanes(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2809,6 +3111,7 @@ int gpc_hip_match_batch_device_packed(gpc_hip_ctx* c, const uint8_t* d_rawL, con
   if (!c || !d_rawL || !d_rawR || !d_packed || !d_rows || !d_counts || npairs <= 0 || cap_per_pair <= 0) return GPC_E_INVALID;
   CHK(check_settings(s));
   if (!s->epipolar_mode || s->use_hashtable) return GPC_E_UNSUPPORTED;  // rows are the unit of the packed form
+  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
   CHK(check_dims(W, H));
   CHK(forest_matches(c, W, H));
   HIPCHK(c, hipSetDevice(c->device));
@@ -2909,6 +3212,7 @@ int gpc_hip_match_pair_begin(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t*
 
 int gpc_hip_match_batch(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, int W, int H, int npairs,
                         const gpc_settings* s, gpc_support* out, int cap, int32_t* counts, int32_t* ncand) {
+  if (c && c->ngroups > 1) return GPC_E_UNSUPPORTED;
   // One pair into a pageable array: the two-step form (results packed over the link, expanded by the workers): 0.20 ms
   // where the chunk pipeline's machinery took 0.27.  (A page-locked array is written by the kernels themselves: below.)
   if (c && npairs == 1 && rawL && rawR && out && counts && cap > 0 && s && !device_view_of_host(out)) {
@@ -3162,6 +3466,7 @@ static int match_batch_packed(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t
 
 int gpc_hip_match_batch_packed(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, int W, int H, int npairs,
                                const gpc_settings* s, uint32_t* packed, int cap, int32_t* rows, int32_t* counts, int32_t* ncand) {
+  if (c && c->ngroups > 1) return GPC_E_UNSUPPORTED;
   const PackedHost ph = {packed, rows};
   const int st = on_gpu_node(c, npairs, [&] { return match_batch_packed(c, rawL, rawR, W, H, npairs, s, nullptr, cap, counts, ncand, &ph); });
   if (c && st != GPC_OK && st != GPC_E_CAPACITY && st != GPC_E_INVALID && st != GPC_E_UNSUPPORTED) {
@@ -3201,10 +3506,12 @@ int gpc_hip_match_pair_begin(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t*
   c->pend.active = false;
   c->pre_slot = -1;
   const size_t n = (size_t)W * H;
-  const int cap_dev = (W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;  // no pair has more supports than an image has candidates
-  const bool packed = s->epipolar_mode && !s->use_hashtable && !c->no_pair_packed;  // (as in match_preprocessed_begin)
+  int cap_dev = (W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;  // no pair has more supports than an image has candidates
+  const bool groups = c->ngroups > 1;   // (group mode: the union stays on the device until match_fetch knows its size)
+  if (groups && s->use_hashtable) return GPC_E_UNSUPPORTED;
+  const bool packed = s->epipolar_mode && !s->use_hashtable && !c->no_pair_packed && !groups;  // (as in match_preprocessed_begin)
   const size_t rows_bytes = pad16(sizeof(int32_t) * (size_t)H);
-  const size_t out_bytes = packed ? rows_bytes + pad16(sizeof(uint32_t) * (size_t)cap_dev) : pad16(sizeof(gpc_support) * (size_t)cap_dev);
+  const size_t out_bytes = groups ? 0 : packed ? rows_bytes + pad16(sizeof(uint32_t) * (size_t)cap_dev) : pad16(sizeof(gpc_support) * (size_t)cap_dev);
   CHK(ensure(c, c->raw, 2 * n));
   CHK(ensure(c, c->codes, sizeof(uint32_t) * n * 2));
   CHK(pinned_counts(c, 1));
@@ -3227,12 +3534,22 @@ int gpc_hip_match_pair_begin(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t*
                      (uint4*)d_l, (uint4*)d_r, n16);
   HIPCHK(c, hipGetLastError());
   CHK(run_preprocess(c, d_l, d_r, W, H, 1, 2, s->gradient_threshold, true));
+  c->pend.dev_out = nullptr;
+  if (groups) {
+    const long cap_u = (long)c->ngroups * (cap_dev - 1) + 1;
+    CHK(ensure(c, c->gdense, sizeof(gpc_support) * (size_t)cap_u));
+    CHK(run_group_match(c, (const uint8_t*)c->smooth.p, (const uint8_t*)c->grad.p, nullptr, W, H, 1, s, 0,
+                        (const uint8_t*)c->grad.p, c->gdense.p, cap_u, d_cnt, d_cnt + 1));
+    cap_dev = (int)std::min(cap_u, (long)INT32_MAX);
+    c->pend.dev_out = c->gdense.p;
+  } else {
   CHK(run_hash(c, (const uint8_t*)c->smooth.p, (const uint8_t*)c->grad.p, nullptr, W, H, 2, false, (uint32_t*)c->codes.p));
   if (packed) {
     const PackedOut po = {reinterpret_cast<int32_t*>(d_arena), (long)cap_dev, (long)H};
     CHK(run_match(c, W, H, 1, s, 2, (const uint8_t*)c->grad.p, d_arena + rows_bytes, cap_dev, d_cnt, d_cnt + 1, &po));
   } else {
     CHK(run_match(c, W, H, 1, s, 0, (const uint8_t*)c->grad.p, d_arena, cap_dev, d_cnt, d_cnt + 1));
+  }
   }
   c->pend.active = true;
   c->pend.direct = false;
@@ -3249,6 +3566,17 @@ int gpc_hip_match_pair(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR,
                        int* n_cand_r) {
   if (!n_out) return GPC_E_INVALID;
   int32_t cnt = 0, nc[2] = {0, 0};
+  if (c && c->ngroups > 1) {  // group mode: always the two-step form (gpc_hip_match_batch refuses group mode)
+    if (cap < 0 || (cap > 0 && !out)) return GPC_E_INVALID;
+    CHK(gpc_hip_match_pair_begin(c, rawL, rawR, W, H, s));
+    int n = 0, nl = 0, nr = 0;
+    const int st1 = match_fetch(c, out, cap, &n, &nl, &nr);
+    c->pend.active = false;
+    *n_out = n;
+    if (n_cand_l) *n_cand_l = nl;
+    if (n_cand_r) *n_cand_r = nr;
+    return st1;
+  }
   const int st = gpc_hip_match_batch(c, rawL, rawR, W, H, 1, s, out, cap, &cnt, nc);
   *n_out = cnt;
   if (n_cand_l) *n_cand_l = nc[0];
@@ -3306,9 +3634,12 @@ int gpc_hip_warmup(gpc_hip_ctx* c, int W, int H, const gpc_settings* settings) {
     if (settings) modes[nmodes++] = *settings;
     else
       for (int k = 0; k < 4; ++k) modes[nmodes++] = gpc_settings{5, 128, 0, (k & 1) ? 0 : 1, (k >> 1) & 1, 1};
-    std::vector<gpc_support> out((size_t)(nm[0] < nm[1] ? nm[0] : nm[1]) + 1);
+    // (group mode: a union holds up to ngroups times as many records; no hash-table matcher, no gpc_hip_match_batch)
+    const bool groups = c->ngroups > 1;
+    std::vector<gpc_support> out(((size_t)(nm[0] < nm[1] ? nm[0] : nm[1]) + 1) * (groups ? c->ngroups : 1));
     const int keep = c->resident_mode, hits = c->resident_hits;
     for (int k = 0; k < nmodes && st == GPC_OK; ++k) {
+      if (groups && modes[k].use_hashtable) continue;
       int ns = 0;
       for (int pass = 0; pass < 2 && st == GPC_OK; ++pass) {  // from the resident images, then the upload path
         c->resident_mode = pass == 0 ? keep : 0;
@@ -3317,8 +3648,8 @@ int gpc_hip_warmup(gpc_hip_ctx* c, int W, int H, const gpc_settings* settings) {
       }
       c->resident_mode = keep;
       int32_t cnt = 0, nc[2];
-      if (st == GPC_OK) st = gpc_hip_match_batch(c, L, R, W, H, 1, &modes[k], pout, (int)cap, &cnt, nc);                 // page-locked
-      if (st == GPC_OK || st == GPC_E_CAPACITY) st = gpc_hip_match_batch(c, sm[0].data(), sm[1].data(), W, H, 1, &modes[k], out.data(), (int)out.size(), &cnt, nc);  // pageable
+      if (st == GPC_OK && !groups) st = gpc_hip_match_batch(c, L, R, W, H, 1, &modes[k], pout, (int)cap, &cnt, nc);     // page-locked
+      if ((st == GPC_OK || st == GPC_E_CAPACITY) && !groups) st = gpc_hip_match_batch(c, sm[0].data(), sm[1].data(), W, H, 1, &modes[k], out.data(), (int)out.size(), &cnt, nc);  // pageable
       if (st == GPC_OK || st == GPC_E_CAPACITY) st = gpc_hip_match_pair_begin(c, sm[0].data(), sm[1].data(), W, H, &modes[k]);   // Forest::matchPair
       if (st == GPC_OK) st = gpc_hip_match_fetch(c, out.data(), (int)out.size(), &ns, nullptr, nullptr);
       if (st == GPC_E_CAPACITY) st = GPC_OK;
