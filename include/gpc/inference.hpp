@@ -25,10 +25,12 @@
 #ifndef GPC_AMD_INFERENCE_HPP
 #define GPC_AMD_INFERENCE_HPP
 
+#include <algorithm>
 #include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 #include <string>
 #include <thread>
@@ -95,7 +97,10 @@ struct ContextHolder {
   bool have_warmed = false;
   std::vector<gpc_filter_mask> uploaded_groups;  // the groups last uploaded (group mode; `have` is false then)
   std::vector<gpc_filter_mask> warmed_groups;
+  uint8_t* seq_frames = nullptr;  // page-locked staging of sequenceMatch's frames (gpc_hip_host_alloc of ctx)
+  size_t seq_cap = 0;
   ~ContextHolder() {
+    if (ctx && seq_frames) gpc_hip_host_free(ctx, seq_frames);
     if (ctx) gpc_hip_destroy(ctx);
   }
 };
@@ -321,6 +326,67 @@ class Forest {
     }
     corr.resize((size_t)n);
     return corr;
+  }
+
+  // Extension (optical flow over a video): stereoMatch(preprocessImage(frames[t]), preprocessImage(frames[t + 1]), ...)
+  // for every consecutive pair, t = 0 .. frames.size() - 2, with each frame preprocessed and hashed once
+  // (gpc_hip_match_sequence).  The frames are staged contiguously in page-locked memory of this thread's context.  Fewer
+  // than two frames, frames of different sizes or a failed call: an empty result (lastStatus() says why).
+  std::vector<std::vector<ndb::Correspondence>> sequenceMatch(std::vector<ndb::Buffer<uint8_t>>& frames, FilterMask& fm,
+                                                              InferenceSettings settings) {
+    typedef std::vector<std::vector<ndb::Correspondence>> Result;
+    if (frames.size() < 2) {
+      detail::fail(GPC_E_INVALID, nullptr, "gpc_hip_match_sequence");
+      return Result();
+    }
+    const int W = frames[0].cols(), H = frames[0].rows(), N = (int)frames.size();
+    for (const ndb::Buffer<uint8_t>& f : frames)
+      if (f.cols() != W || f.rows() != H) {
+        detail::fail(GPC_E_INVALID, nullptr, "gpc_hip_match_sequence");
+        return Result();
+      }
+    detail::ContextHolder& h = detail::holder();
+    if (!h.ctx || !upload(h, fm)) return Result();
+    const size_t n = (size_t)W * H, bytes = n * N;
+    if (bytes > h.seq_cap) {
+      if (h.seq_frames) gpc_hip_host_free(h.ctx, h.seq_frames);
+      h.seq_frames = nullptr;
+      h.seq_cap = 0;
+      void* p = nullptr;
+      const int st = gpc_hip_host_alloc(h.ctx, bytes, &p);
+      if (st != GPC_OK) {
+        detail::fail(st, h.ctx, "gpc_hip_host_alloc");
+        return Result();
+      }
+      h.seq_frames = static_cast<uint8_t*>(p);
+      h.seq_cap = bytes;
+    }
+    for (int f = 0; f < N; ++f) memcpy(h.seq_frames + (size_t)f * n, frames[f].data(), n);
+    const gpc_settings s = settings.toC();
+    // no match of two candidate lists has more results than the shorter list: a quarter of the pixels first, the true
+    // largest count when that did not fit
+    int cap = (int)std::max<size_t>(1024, n / 4);
+    std::vector<gpc_correspondence> out;
+    std::vector<int32_t> counts((size_t)N - 1);
+    int st = GPC_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      out.resize((size_t)cap * (N - 1));
+      st = gpc_hip_match_sequence(h.ctx, h.seq_frames, W, H, N, &s, out.data(), cap, counts.data(), nullptr);
+      if (st != GPC_E_CAPACITY) break;
+      cap = *std::max_element(counts.begin(), counts.end());
+    }
+    if (st != GPC_OK) {
+      detail::fail(st, h.ctx, "gpc_hip_match_sequence");
+      return Result();
+    }
+    Result r((size_t)N - 1);
+    for (int t = 0; t < N - 1; ++t) {
+      const gpc_correspondence* c = out.data() + (size_t)t * cap;
+      r[t].reserve((size_t)counts[t]);
+      for (int i = 0; i < counts[t]; ++i)
+        r[t].push_back(ndb::Correspondence(ndb::Point(c[i].src_x, c[i].src_y), ndb::Point(c[i].tar_x, c[i].tar_y)));
+    }
+    return r;
   }
 
   // inference.hpp:375-393

@@ -285,6 +285,32 @@ int gpc_hip_fed_calls(const gpc_hip_ctx* ctx);
 /* The NUMA node of the host this context's GPU hangs off (the expansion workers are bound to its CPUs), -1 if unknown. */
 int gpc_hip_host_numa_node(const gpc_hip_ctx* ctx);
 
+/* ---- frame sequences (optical flow) ------------------------------------------ */
+/* Forest::stereoMatch of every consecutive pair (f[t], f[t+1]) of a frame sequence already in HBM ([nframes][height][width]);
+ * d_out[nframes-1][cap_per_pair], d_counts[nframes-1] true counts, d_ncand[nframes] (optional) candidates per FRAME.
+ * Record t is what stereoMatch(preprocessImage(f[t]), preprocessImage(f[t+1]), fm, settings) returns, in its order, for
+ * every matcher (epipolar_mode 0 / 1 x use_hashtable 0 / 1) and either arithmetic.  Every frame is preprocessed and hashed
+ * once: one k_preprocess and one k_hash launch over the nframes images, the joins read pair t's images at frames t, t + 1.
+ * Waiting is as for gpc_hip_match_batch_device: with epipolar_mode = 1 and use_hashtable = 0 the call only queues work on
+ * the context's stream; the device-wide matchers (epipolar_mode = 0 or use_hashtable = 1) wait on the host once inside
+ * the call.  The outputs may be read after gpc_hip_synchronize (or another wait on the stream).
+ * A pair with more than cap_per_pair records: GPC_E_CAPACITY, true counts, each pair's first cap_per_pair records valid.
+ * nframes < 2, null pointers or a bad size: GPC_E_INVALID; no forest: GPC_E_NO_FOREST; group mode (ngroups > 1):
+ * GPC_E_UNSUPPORTED.  With two lanes (gpc_hip_set_pipeline(ctx, 2)) the lanes are drained and the call runs on the
+ * context's stream. */
+int gpc_hip_match_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int width, int height, int nframes,
+                                  const gpc_settings* settings, gpc_correspondence* d_out, int cap_per_pair,
+                                  int32_t* d_counts, int32_t* d_ncand);
+/* The same from / to host memory (pageable or page-locked), synchronous.  The frames go through the device in chunks of
+ * at most 16 frames (15 pairs); consecutive chunks share one frame, which is uploaded, preprocessed and hashed again in
+ * the next chunk (1/15 more of that work for long sequences).  While chunk k is matched, chunk k+1 is uploaded on a
+ * stream of its own.  Pageable frames pass through the context's page-locked arena: a _begin call still pending on the
+ * context is waited for first and then ended, as every later call on the context ends it (its _fetch returns
+ * GPC_E_INVALID).  ncand[nframes] is optional. */
+int gpc_hip_match_sequence(gpc_hip_ctx* ctx, const uint8_t* frames, int width, int height, int nframes,
+                           const gpc_settings* settings, gpc_correspondence* out, int cap_per_pair,
+                           int32_t* counts, int32_t* ncand);
+
 /* ---- packed results ------------------------------------------------------------ */
 /* Forest::rectifiedMatch (inference.hpp:375-393) in epipolar mode emits supports row by row, so a support
  * {x, y, float(x - xR)} (ndb::Support, buffer.hpp:91-97) is fully described by one 32-bit word x | xR << 16 plus

@@ -84,6 +84,7 @@ SYMBOLS = [
     "gpc_hip_train_eval_split", "gpc_hip_train_mark_split_samples", "gpc_hip_train_fern",
     "gpc_hip_train_begin_fern", "gpc_hip_train_eval_level", "gpc_hip_train_commit_level",
     "gpc_hip_extract_triplets", "gpc_hip_extract_triplets_device", "gpc_hip_train_set_read",
+    "gpc_hip_match_sequence_device", "gpc_hip_match_sequence",
 ]
 
 
@@ -141,6 +142,9 @@ def load():
                                              C.POINTER(Settings), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.gpc_hip_match_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(Settings), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.gpc_hip_match_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings),
+                                                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.gpc_hip_match_sequence.argtypes = L.gpc_hip_match_sequence_device.argtypes
     L.gpc_hip_match_batch_device_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(Settings), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                     C.c_void_p]
@@ -551,6 +555,31 @@ class Context:
         self._ck(self.L.gpc_hip_match_batch_device_packed(self.h, C.c_void_p(d_rawL), C.c_void_p(d_rawR), width, height,
                                                           npairs, C.byref(settings), C.c_void_p(d_packed), cap_per_pair,
                                                           C.c_void_p(d_rows), C.c_void_p(d_counts), C.c_void_p(d_ncand or 0)))
+
+    # ---- frame sequences (optical flow): Forest::stereoMatch of every consecutive pair, each frame hashed once
+    def match_sequence(self, frames, settings, cap=None):
+        """frames: uint8 [N, H, W] in host memory (N >= 2) -> (records [N-1, cap] of CORR_DTYPE, true counts [N-1],
+        candidate counts per frame [N], status).  Row t holds the first min(counts[t], cap) correspondences of the pair
+        (frames[t], frames[t+1])."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        if frames.ndim != 3:
+            raise ValueError("frames must be [N, H, W]")
+        N, H, W = frames.shape
+        cap = cap if cap is not None else W * H
+        out = np.empty((max(N - 1, 1), max(cap, 1)), CORR_DTYPE)
+        counts = np.zeros(max(N - 1, 1), np.int32)
+        ncand = np.zeros(N, np.int32)
+        st = self.L.gpc_hip_match_sequence(self.h, _ptr(frames), W, H, N, C.byref(settings), _ptr(out), cap,
+                                           _ptr(counts), _ptr(ncand))
+        self._ck(st, allow=(E_CAPACITY,))
+        return out, counts, ncand, st
+
+    def match_sequence_device(self, d_frames, width, height, nframes, settings, d_out, cap_per_pair, d_counts, d_ncand=0):
+        """Frames [nframes][height][width] in HBM -> d_out[nframes-1][cap_per_pair] correspondences, d_counts[nframes-1],
+        d_ncand[nframes] (optional); asynchronous as match_batch_device."""
+        self._ck(self.L.gpc_hip_match_sequence_device(self.h, C.c_void_p(d_frames), width, height, nframes,
+                                                      C.byref(settings), C.c_void_p(d_out), cap_per_pair,
+                                                      C.c_void_p(d_counts), C.c_void_p(d_ncand or 0)))
 
     # ---- fern training: the scoring loop
     def train_set(self, triplets):

@@ -233,6 +233,7 @@ struct gpc_hip_ctx {
   bool gtau = false;           // one of the groups has a nonzero tau
   DevBuf gforest_dev;          // [3][GPC_MAX_GROUPS] GpcForestDev: SSE order, Naive order, SSE with the tall tile's offsets
   DevBuf vstats, vcand, vout, vcnt, vncand, uplane, ublk, gdense;  // virtual-pair statistics / candidates / results, union state
+  DevBuf sstats;  // frame sequences: the frames' statistics expanded into the pair layout [npairs*2] (k_seq_stats)
 
   // workspaces
   DevBuf raw, smooth, grad, candmap, codes, staged, rowcnt, stats, out, counts, ncand, mask;
@@ -286,6 +287,7 @@ struct gpc_hip_ctx {
   // (allocated by the call, released before it returns)
   DevBuf ext_raw, ext_smooth, ext_grad, ext_groups;
   int extract_frames = 0;     // GPC_HIP_EXTRACT_FRAMES: frame pairs per chunk (tests; default: 64 MiB of smoothed frames)
+  int seq_frames = 0;         // GPC_HIP_SEQ_FRAMES: frames per chunk of gpc_hip_match_sequence (tests; default 16)
 
   // Forest::preprocessImage -> Forest::rectifiedMatch without the round trip (the reference's PreprocessedImage travels by
   // value through host memory, inference.hpp:161-165): the last two preprocessed images stay on the device beside the
@@ -656,10 +658,12 @@ bool next_int(const char*& p, int& v) {
 
 // ---------------------------------------------------------------- pipeline stages
 
+// seq: the code images (and candidate bytes) are a frame sequence [npairs + 1][H][W], pair p = frames (p, p + 1); the
+// statistics are in the pair layout all the same (k_seq_stats)
 int run_global_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, int mode, const uint8_t* d_cand,
-                     void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand);
+                     void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand, bool seq = false);
 int run_hashtable_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, int mode, const uint8_t* d_cand,
-                        void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand);
+                        void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand, bool seq = false);
 
 // raw0/raw1 device pointers; fills smooth, grad for npairs*sides images
 // gradbits: the caller's only reader of the gradient image is run_hash (a batched pipeline): it may leave as one bit per pixel
@@ -973,11 +977,14 @@ int ensure_aux_stream(gpc_hip_ctx* c) {
 // code images of npairs pairs -> supports / correspondences in d_out.
 // d_cand: the candidate bytes the hash kernel used ([2*npairs][H][W]: grad, or the scattered mask list)
 // mode 0: gpc_support, 1: gpc_correspondence, 2: packed supports (epipolar sort-match only; `po` says where)
+// seq: a frame sequence (codes / d_cand [npairs + 1][H][W], pair p = frames p and p + 1; statistics in the pair layout):
+// the epipolar matcher takes k_row_join_seq + k_gather_rows, the device-wide matchers read the images at a stride of one
 int run_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, int mode, const uint8_t* d_cand,
-              void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand, const PackedOut* po = nullptr) {
+              void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand, const PackedOut* po = nullptr, bool seq = false) {
   const int apply_filter = (mode != 1);
   if (mode == 2 && (s->use_hashtable || !s->epipolar_mode || !po)) return GPC_E_UNSUPPORTED;
-  if (s->use_hashtable) return run_hashtable_match(c, W, H, npairs, s, mode, d_cand, d_out, cap, d_counts, d_ncand);
+  if (seq && (mode == 2 || po)) return GPC_E_UNSUPPORTED;
+  if (s->use_hashtable) return run_hashtable_match(c, W, H, npairs, s, mode, d_cand, d_out, cap, d_counts, d_ncand, seq);
   if (s->epipolar_mode) {
     CHK(ensure(c, c->staged, sizeof(uint32_t) * (size_t)W * H * npairs));
     CHK(ensure(c, c->rowcnt, sizeof(int32_t) * (size_t)H * npairs * 2));
@@ -989,7 +996,7 @@ int run_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, i
     // One launch for join + output (k_rowjoin_fused.h) for rows up to 4096 px (12 bits of x beside the flags) when the
     // records' place follows from the rows before them alone (not the gap-free packing of `totals`)
     const size_t flds = RJF_LDS_BYTES(jp.nt * jp.spt);
-    bool fuse = !c->no_fuse && npairs >= c->fuse_min_pairs && jp.spt <= 4 && jp.nt * jp.spt <= 4096 &&
+    bool fuse = !seq && !c->no_fuse && npairs >= c->fuse_min_pairs && jp.spt <= 4 && jp.nt * jp.spt <= 4096 &&
                 !(po && po->totals) && (long)npairs * (H - 2 * GPC_R) < (1l << 31) - 65536;
     if (fuse && !c->fuse_always) {
       // The persistent launch pays off once every workgroup takes several rows (its output lags one row behind, and the
@@ -1083,17 +1090,19 @@ int run_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, i
       const int rpw = 1;  // (the kernel takes one row per workgroup)
       const dim3 jgrid((H - 2 * GPC_R + rpw - 1) / rpw, npairs);
       const bool wide = wide_codes(c);
-      snprintf(c->launch_name[KID_ROW_JOIN], sizeof c->launch_name[0], "gpc::k_row_join<%d, %d, %s>", jp.spt, jp.nt,
-               wide ? "true" : "false");
-#define LAUNCH_JOIN(SPT, NT, WIDE)                                                                            \
+      snprintf(c->launch_name[KID_ROW_JOIN], sizeof c->launch_name[0], "gpc::k_row_join%s<%d, %d, %s>", seq ? "_seq" : "",
+               jp.spt, jp.nt, wide ? "true" : "false");
+#define LAUNCH_JOIN_K(K, SPT, NT, WIDE)                                                                       \
   do {                                                                                                        \
-    const void* fn_ = reinterpret_cast<const void*>(gpc::k_row_join<SPT, NT, WIDE>);                          \
+    const void* fn_ = reinterpret_cast<const void*>(gpc::K<SPT, NT, WIDE>);                                   \
     if (jp.lds > 48 * 1024) CHK(allow_dyn_lds(c, fn_, jp.lds));                                               \
-    hipLaunchKernelGGL((gpc::k_row_join<SPT, NT, WIDE>), jgrid, dim3(NT), jp.lds, c->stream,                  \
+    hipLaunchKernelGGL((gpc::K<SPT, NT, WIDE>), jgrid, dim3(NT), jp.lds, c->stream,                           \
                        (const uint32_t*)c->codes.p, d_cand, W, H, disp_high, apply_filter,                    \
                        (const int32_t*)c->stats.p, (uint32_t*)c->staged.p, (int32_t*)c->rowcnt.p, jp.log2s,   \
                        rpw, gpc::RjVirt());                                                    \
   } while (0)
+#define LAUNCH_JOIN(SPT, NT, WIDE) \
+  do { if (seq) LAUNCH_JOIN_K(k_row_join_seq, SPT, NT, WIDE); else LAUNCH_JOIN_K(k_row_join, SPT, NT, WIDE); } while (0)
 #define LAUNCH_JOIN_W(SPT, NT) do { if (wide) LAUNCH_JOIN(SPT, NT, true); else LAUNCH_JOIN(SPT, NT, false); } while (0)
 #define LAUNCH_JOIN_S(NT)                      \
   switch (jp.spt) {                            \
@@ -1110,6 +1119,7 @@ int run_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, i
 #undef LAUNCH_JOIN_S
 #undef LAUNCH_JOIN_W
 #undef LAUNCH_JOIN
+#undef LAUNCH_JOIN_K
       HIPCHK(c, hipGetLastError());
     }
     {
@@ -1128,7 +1138,7 @@ int run_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, i
     }
     return GPC_OK;
   }
-  return run_global_match(c, W, H, npairs, s, mode, d_cand, d_out, cap, d_counts, d_ncand);
+  return run_global_match(c, W, H, npairs, s, mode, d_cand, d_out, cap, d_counts, d_ncand, seq);
 }
 
 // Shared set-up of the two device-wide-sort matchers (k_global.h, k_hashtable.h); every launch
@@ -1140,7 +1150,7 @@ struct GlobalPlan {
   size_t esz;
 };
 
-int plan_global(gpc_hip_ctx* c, int W, int H, int npairs, int mode, int cap, bool hashtable, GlobalPlan& g) {
+int plan_global(gpc_hip_ctx* c, int W, int H, int npairs, int mode, int cap, bool hashtable, GlobalPlan& g, bool seq) {
   const size_t n = (size_t)W * H;
   g.nmax = 2 * (W - 2 * GPC_R) * (H - 2 * GPC_R);
   g.nblk = (g.nmax + GS_TILE - 1) / GS_TILE;
@@ -1163,7 +1173,7 @@ int plan_global(gpc_hip_ctx* c, int W, int H, int npairs, int mode, int cap, boo
   g.blkcnt = g.hist + (size_t)256 * g.nblk * npairs;
   g.gmisc = (int32_t*)c->gmisc.p;
   g.rowcnt = (int32_t*)c->rowcnt.p;
-  g.bs.codes = (long)(2 * n);
+  g.bs.codes = (long)((seq ? 1 : 2) * n);  // (a sequence: pair p's images are frames p and p + 1)
   g.bs.recs = g.nmax;
   g.bs.hist = (long)256 * g.nblk;
   g.bs.blk = g.nmblk;
@@ -1346,9 +1356,9 @@ int run_partition_match(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, int n
 }
 
 int run_global_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, int mode, const uint8_t* d_cand,
-                     void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand) {
+                     void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand, bool seq) {
   GlobalPlan g;
-  CHK(plan_global(c, W, H, npairs, mode, cap, false, g));
+  CHK(plan_global(c, W, H, npairs, mode, cap, false, g, seq));
   if (!c->no_partition) {
     bool done = false;
     CHK(run_partition_match(c, g, W, H, npairs, s, mode, d_cand, d_out, cap, d_counts, d_ncand, &done));
@@ -1565,9 +1575,9 @@ int run_hashtable_partition(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, i
 
 // useHashtable mode (hashmatch.hpp): stable radix sort by bucket id + one thread per bucket (k_hashtable.h)
 int run_hashtable_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, int mode, const uint8_t* d_cand,
-                        void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand) {
+                        void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand, bool seq) {
   GlobalPlan g;
-  CHK(plan_global(c, W, H, npairs, mode, cap, true, g));
+  CHK(plan_global(c, W, H, npairs, mode, cap, true, g, seq));
   if (!c->no_partition) {
     bool done = false;
     CHK(run_hashtable_partition(c, g, W, H, npairs, s, mode, d_cand, d_out, cap, d_counts, d_ncand, &done));
@@ -1863,6 +1873,19 @@ __global__ void k_stats_init(int32_t* __restrict__ stats, int nimg) {
   stats[i * GPC_STAT_STRIDE + GPC_STAT_CODEOR] = 0;
   stats[i * GPC_STAT_STRIDE + 3] = 0;
 }
+
+// Frame sequences: the statistics of nframes frames -> the pair layout the joins read (image 2p + s of pair p = frame
+// p + s), and the candidate count of every frame into ncand[nframes] (optional).  One thread per word.
+__global__ void k_seq_stats(const int32_t* __restrict__ fstats, int32_t* __restrict__ pstats, int32_t* __restrict__ ncand,
+                            int nframes) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int nwords = 2 * (nframes - 1) * GPC_STAT_STRIDE;
+  if (i < nwords) {
+    const int img = i / GPC_STAT_STRIDE, k = i - img * GPC_STAT_STRIDE;
+    pstats[i] = fstats[((img >> 1) + (img & 1)) * GPC_STAT_STRIDE + k];
+  }
+  if (ncand && i < nframes) ncand[i] = fstats[i * GPC_STAT_STRIDE + GPC_STAT_NCAND];
+}
 }  // namespace gpc
 
 namespace {
@@ -2014,6 +2037,10 @@ int gpc_hip_create(int device, gpc_hip_ctx** out) {
   }
   const char* ck = getenv("GPC_HIP_CHUNK");
   if (ck && atoi(ck) > 0 && atoi(ck) <= 1024) c->chunk_pairs = atoi(ck);
+  if (const char* e = getenv("GPC_HIP_SEQ_FRAMES")) {
+    const int v = atoi(e);
+    if (v >= 2 && v <= 1024) c->seq_frames = v;
+  }
   const char* et = getenv("GPC_HIP_EXPAND_THREADS");
   if (et && atoi(et) > 0 && atoi(et) <= 64) c->expand_threads = atoi(et);
   if (const char* e = getenv("GPC_HIP_UPLOAD")) c->upload_mode = atoi(e);
@@ -2078,7 +2105,8 @@ int gpc_hip_destroy(gpc_hip_ctx* c) {
                     &c->stats, &c->out, &c->counts, &c->ncand, &c->mask, &c->gkeys[0], &c->gkeys[1],
                     &c->gvals[0], &c->gvals[1], &c->ghist, &c->gmisc, &c->hkeys[0], &c->hkeys[1],
                     &c->hvals[0], &c->hvals[1], &c->hrec, &c->forest_dev, &c->packed, &c->gpart, &c->jstate, &c->gkv,
-                    &c->res_smooth, &c->res_grad, &c->ext_raw, &c->ext_smooth, &c->ext_grad, &c->ext_groups};
+                    &c->res_smooth, &c->res_grad, &c->ext_raw, &c->ext_smooth, &c->ext_grad, &c->ext_groups,
+                    &c->sstats};
   while (!c->train_sets.empty()) (void)gpc_hip_train_set_destroy(c, c->train_sets.back());
   for (DevBuf* b : bufs) release(*b);
   for (auto& s : c->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -3102,6 +3130,134 @@ static int match_batch_unpacked(gpc_hip_ctx* c, const uint8_t* rawL, const uint8
   HIPCHK(c, hipStreamSynchronize(c->s_cnt));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   CHK(check_join_err(c));
+  return status;
+}
+
+// ------------------------------------------------------------------ frame sequences
+
+// nframes frames in HBM -> the correspondences of the nframes - 1 consecutive pairs.  One k_preprocess and one k_hash over
+// the frames (sides = 1: image f = frame f); k_seq_stats expands the frames' statistics into the pair layout, which stands
+// in for the context's statistics while the matcher runs (pair p reads the code images of frames p and p + 1).
+int gpc_hip_match_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W, int H, int nframes, const gpc_settings* s,
+                                  gpc_correspondence* d_out, int cap_per_pair, int32_t* d_counts, int32_t* d_ncand) {
+  if (!c || !d_frames || !d_out || !d_counts || nframes < 2 || cap_per_pair <= 0) return GPC_E_INVALID;
+  CHK(check_settings(s));
+  CHK(check_dims(W, H));
+  CHK(forest_matches(c, W, H));
+  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->pipeline > 1) CHK(drain_lanes(c));  // (sequences run on the context itself)
+  const size_t n = (size_t)W * H;
+  const int npairs = nframes - 1;
+  CHK(ensure(c, c->codes, sizeof(uint32_t) * n * nframes));
+  CHK(ensure(c, c->sstats, sizeof(int32_t) * GPC_STAT_STRIDE * 2 * npairs));
+  CHK(run_preprocess(c, d_frames, nullptr, W, H, nframes, 1, s->gradient_threshold, true));
+  CHK(run_hash(c, (const uint8_t*)c->smooth.p, (const uint8_t*)c->grad.p, nullptr, W, H, nframes, false, (uint32_t*)c->codes.p));
+  const int nthr = 2 * npairs * GPC_STAT_STRIDE;  // (>= nframes)
+  hipLaunchKernelGGL(gpc::k_seq_stats, dim3((nthr + 255) / 256), dim3(256), 0, c->stream, (const int32_t*)c->stats.p,
+                     (int32_t*)c->sstats.p, d_ncand, nframes);
+  HIPCHK(c, hipGetLastError());
+  std::swap(c->stats, c->sstats);
+  const int st = run_match(c, W, H, npairs, s, 1, (const uint8_t*)c->grad.p, d_out, cap_per_pair, d_counts, nullptr, nullptr,
+                           true);
+  std::swap(c->stats, c->sstats);
+  return st;
+}
+
+// Host frames in, correspondences out, in chunks of at most K frames (consecutive chunks share a frame): chunk k + 1 is
+// uploaded on the batch pipeline's input stream while chunk k is matched on the context's stream; the counts of a chunk
+// come back on the counts stream, and its records are fetched once they are known.
+int gpc_hip_match_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, int nframes, const gpc_settings* s,
+                           gpc_correspondence* out, int cap, int32_t* counts, int32_t* ncand) {
+  if (!c || !frames || !out || !counts || nframes < 2 || cap <= 0) return GPC_E_INVALID;
+  CHK(check_settings(s));
+  CHK(check_dims(W, H));
+  CHK(forest_matches(c, W, H));
+  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->pend.active || c->pre_slot >= 0) {
+    // what a _begin queued may still be writing its results into the page-locked arena this call fills with frames:
+    // it is waited for, and ended as every later call on the context ends it
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->pend.active = false;
+    c->pre_slot = -1;
+  }
+  if (c->pipeline > 1) CHK(drain_lanes(c));
+  const size_t n = (size_t)W * H;
+  const int npairs = nframes - 1;
+  const int K = c->seq_frames > 0 ? c->seq_frames : 16;
+  const int step = K - 1;                                   // frames a chunk moves on
+  const int nch = (npairs + step - 1) / step;
+  const int kf = nframes < K ? nframes : K;                 // frames of the largest chunk
+  const size_t slot = pad16(n * kf);
+  CHK(batch_streams(c));
+  CHK(pinned_counts(c, nframes));                           // counts [npairs] + candidates per frame [nframes]
+  CHK(ensure(c, c->raw, 2 * slot));
+  CHK(ensure(c, c->out, sizeof(gpc_correspondence) * (size_t)cap * npairs));
+  CHK(ensure(c, c->counts, sizeof(int32_t) * npairs));
+  CHK(ensure(c, c->ncand, sizeof(int32_t) * nframes));
+  const bool bounce = !device_view_of_host(frames);
+  uint8_t* h_arena = nullptr;
+  if (bounce) {  // pageable frames: two slots of the page-locked arena
+    uint8_t* d_arena = nullptr;
+    CHK(xfer_reserve(c, 2 * slot, &d_arena));
+    h_arena = c->h_xfer;
+    CHK(ensure_pool(c));
+  }
+  int32_t* hc = c->h_cnt;
+  int32_t* hn = c->h_cnt + npairs;
+  gpc_correspondence* d_out = (gpc_correspondence*)c->out.p;
+  auto first = [&](int k) { return k * step; };
+  auto frames_of = [&](int k) { return nframes - first(k) < K ? nframes - first(k) : K; };
+  auto upload = [&](int k) -> int {
+    const int sl = k & 1, f0 = first(k), fc = frames_of(k);
+    uint8_t* d_in = (uint8_t*)c->raw.p + (size_t)sl * slot;
+    if (k >= 2) HIPCHK(c, hipStreamWaitEvent(c->s_in, c->e_comp[sl], 0));  // chunk k-2 has read this slot
+    const uint8_t* src = frames + (size_t)f0 * n;
+    if (bounce) {
+      uint8_t* b = h_arena + (size_t)sl * slot;
+      if (k >= 2) HIPCHK(c, hipEventSynchronize(c->e_in[sl]));  // the upload of chunk k-2 has left this arena slot
+      host_copy(c, b, src, n * fc, true);
+      host_copy_wait(c);
+      src = b;
+    }
+    HIPCHK(c, hipMemcpyAsync(d_in, src, n * fc, hipMemcpyHostToDevice, c->s_in));
+    HIPCHK(c, hipEventRecord(c->e_in[sl], c->s_in));
+    return GPC_OK;
+  };
+  int status = GPC_OK;
+  auto collect = [&](int k) -> int {
+    const int p0 = first(k), pc = frames_of(k) - 1;
+    HIPCHK(c, hipEventSynchronize(c->e_cnt[k & 1]));
+    memcpy(counts + p0, hc + p0, sizeof(int32_t) * pc);
+    for (int p = p0; p < p0 + pc; ++p) {
+      const int ncopy = counts[p] < cap ? counts[p] : cap;
+      if (counts[p] > cap) status = GPC_E_CAPACITY;
+      if (ncopy > 0)
+        HIPCHK(c, hipMemcpyAsync(out + (size_t)p * cap, d_out + (size_t)p * cap, sizeof(gpc_correspondence) * (size_t)ncopy,
+                                 hipMemcpyDeviceToHost, c->s_out));
+    }
+    return GPC_OK;
+  };
+  CHK(upload(0));
+  for (int k = 0; k < nch; ++k) {
+    const int sl = k & 1, f0 = first(k), fc = frames_of(k);
+    if (k + 1 < nch) CHK(upload(k + 1));  // (queued before this chunk's matcher: the device-wide ones wait on the host)
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->e_in[sl], 0));
+    CHK(gpc_hip_match_sequence_device(c, (const uint8_t*)c->raw.p + (size_t)sl * slot, W, H, fc, s, d_out + (size_t)f0 * cap,
+                                      cap, (int32_t*)c->counts.p + f0, (int32_t*)c->ncand.p + f0));
+    HIPCHK(c, hipEventRecord(c->e_comp[sl], c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->s_cnt, c->e_comp[sl], 0));
+    HIPCHK(c, hipMemcpyAsync(hc + f0, (int32_t*)c->counts.p + f0, sizeof(int32_t) * (fc - 1), hipMemcpyDeviceToHost, c->s_cnt));
+    HIPCHK(c, hipMemcpyAsync(hn + f0, (int32_t*)c->ncand.p + f0, sizeof(int32_t) * fc, hipMemcpyDeviceToHost, c->s_cnt));
+    HIPCHK(c, hipEventRecord(c->e_cnt[sl], c->s_cnt));
+    if (k >= 1) CHK(collect(k - 1));
+  }
+  CHK(collect(nch - 1));
+  HIPCHK(c, hipStreamSynchronize(c->s_out));
+  HIPCHK(c, hipStreamSynchronize(c->s_cnt));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (ncand) memcpy(ncand, hn, sizeof(int32_t) * nframes);
   return status;
 }
 
