@@ -11,8 +11,10 @@
  * raw/smooth/grad/mask/codes/supports produced by the compiled reference) are
  * committed as tests/golden/appendix_c.json and checked by
  * tests/test_oracle_golden.py; the raw-pointer kernels are additionally checked
- * against the real reference kernels (oracle/_ref, built from
- * /root/reference/lib/gpc/filter.hpp where it lies) by tests/test_oracle_vs_ref.py.
+ * against the real reference kernels (oracle/_ref, built from the reference's
+ * lib/gpc/filter.hpp where it lies) by tests/test_oracle_vs_ref.py, and the glue
+ * between them against the reference's own Forest class (oracle/ref_full_harness.cpp)
+ * by tests/test_oracle_vs_ref_full.py.
  */
 #ifndef GPC_ORACLE_H
 #define GPC_ORACLE_H

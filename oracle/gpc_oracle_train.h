@@ -2,9 +2,10 @@
  *
  * TEST INFRASTRUCTURE ONLY (tests/, __graft_entry__.smoke(), bench tools' CPU leg); never shipped.
  *
- * PARITY UNPINNED: the reference has no tests or golden vectors for training, and Fern.hpp /
- * Feature.hpp cannot be compiled here (they need Eigen, which this image lacks), so this
- * restatement is checked against nothing but itself and a plain numpy model in tests/.
+ * Parity pin: Fern::evalSplit, Fern::markSplitSamples and Feature::getDecisions of the reference,
+ * compiled where they lie (oracle/ref_full_harness.cpp), in tests/test_oracle_vs_ref_full.py, and
+ * their recorded results in tests/golden/ref_full_vectors.json; the random search of Fern::train is
+ * checked against a plain numpy model only (its generator is the standard library's).
  * Every function cites the reference lines it follows.
  */
 #ifndef GPC_ORACLE_TRAIN_H

@@ -1,5 +1,6 @@
 """ctypes front-end for the CPU oracle (oracle/libgpc_oracle.so) and, when built,
-the real reference kernels (oracle/_ref/libgpc_ref.so).
+the real reference kernels (oracle/_ref/libgpc_ref.so) and the reference's own classes
+(oracle/_ref/libgpc_ref_full.so).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py.  The product package (opengpc_amd/) never imports it.
@@ -15,6 +16,8 @@ ORACLE_SO = os.path.join(HERE, "libgpc_oracle.so")
 ORACLE_FAST_SO = os.path.join(HERE, "libgpc_oracle_fast.so")
 REF_SO = os.path.join(HERE, "_ref", "libgpc_ref.so")
 REF_NAIVE_SO = os.path.join(HERE, "_ref", "libgpc_ref_naive.so")
+REF_FULL_SO = os.path.join(HERE, "_ref", "libgpc_ref_full.so")
+REF_FULL_NAIVE_SO = os.path.join(HERE, "_ref", "libgpc_ref_full_naive.so")
 MAX_TESTS = 32
 
 
@@ -93,7 +96,7 @@ class Oracle:
         L.gpc_oracle_rectified_filter.restype = C.c_int
         L.gpc_oracle_match_pair.restype = C.c_int
 
-    # ---- training scoring loop (parity unpinned, see gpc_oracle_train.h)
+    # ---- training scoring loop (pinned to Fern.hpp, see gpc_oracle_train.h)
     def eval_split(self, triplets, marks, params, score_until_level, w1):
         """Fern::evalSplit.  triplets: (n, 3, 729) u8; marks: (n,) u8; params: SPLIT_DTYPE array."""
         t = np.ascontiguousarray(triplets, np.uint8)
@@ -371,3 +374,163 @@ class Ref:
         out = np.empty((max(len(ss), len(ts), 1), 2), np.int32)
         n = self.lib.gpc_ref_hashmatch(_u64p(ss), _i32p(sk), len(ss), _u64p(ts), _i32p(tk), len(ts), _i32p(out))
         return out[:n].copy()
+
+
+class _MatchOut(C.Structure):
+    _fields_ = [("states_l", C.c_void_p), ("states_r", C.c_void_p), ("corr", C.c_void_p), ("n_corr", C.c_void_p),
+                ("supp_xy", C.c_void_p), ("supp_d", C.c_void_p), ("n_supp", C.c_void_p),
+                ("sorted_t_state", C.c_void_p), ("sorted_t_xy", C.c_void_p)]
+
+
+class RefMatch:
+    """What one reference matching call produced, level by level (RefFull.match_pair / match_pre)."""
+
+    def __init__(self, rc, mask_l, mask_r, states_l, states_r, corr, supp, sorted_t_state, sorted_t_xy):
+        self.undefined = rc == 1          # sort matcher, sources but no target candidate: nothing was run
+        self.mask_l, self.mask_r = mask_l, mask_r
+        self.states_l, self.states_r = states_l, states_r   # evalFastMaskOnSubsetSSE, mask order
+        self.corr = corr                  # stereoMatch, CORR_DTYPE
+        self.supp = supp                  # rectifiedMatch, SUPPORT_DTYPE
+        self.sorted_t_state = sorted_t_state   # sort matcher: the target array as the reference's sort left it
+        self.sorted_t_xy = sorted_t_xy
+
+
+class RefFull:
+    """The reference's own Forest / Fern / Feature / Buffer classes (inference.hpp, training.hpp,
+    buffer.hpp) behind oracle/ref_full_harness.cpp, when oracle/_ref is built.  Widths are multiples of 16."""
+
+    def __init__(self, naive=False):
+        path = REF_FULL_NAIVE_SO if naive else REF_FULL_SO
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        self.naive = naive
+        self.lib = L = C.CDLL(path)
+        for name in ("is_sse", "read_forest", "preprocess", "match_pre", "match_pair", "find_correspondences",
+                     "disparity_vis"):
+            getattr(L, "gpc_reff_" + name).restype = C.c_int
+        assert L.gpc_reff_is_sse() == (0 if naive else 1)
+
+    @staticmethod
+    def available(naive=False):
+        return os.path.exists(REF_FULL_NAIVE_SO if naive else REF_FULL_SO)
+
+    def read_forest(self, path, W, H):
+        """(offsets, taus, type) as Forest::readForest returns them; a zero forest has no taus."""
+        offs, taus = np.zeros(64, np.int32), np.zeros(32, np.int32)
+        no, nt, ty = C.c_int32(), C.c_int32(), C.c_int32()
+        rc = self.lib.gpc_reff_read_forest(path.encode(), W, H, _i32p(offs), _i32p(taus), C.byref(no), C.byref(nt),
+                                           C.byref(ty))
+        assert rc == 0, rc
+        return offs[:no.value].copy(), taus[:nt.value].copy(), ty.value
+
+    def preprocess(self, raw, thr):
+        raw = np.ascontiguousarray(raw)
+        H, W = raw.shape
+        smooth, grad = np.empty((H, W), np.uint8), np.empty((H, W), np.uint8)
+        mask = np.empty(H * W, np.int32)
+        n = self.lib.gpc_reff_preprocess(_u8p(raw), W, H, int(thr), _u8p(smooth), _u8p(grad), _i32p(mask))
+        assert n >= 0, n
+        return smooth, grad, mask[:n].copy()
+
+    def _run(self, cap, call):
+        sl, sr = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+        corr, supp_xy, supp_d = np.zeros((cap, 4), np.int32), np.zeros((cap, 2), np.int32), np.zeros(cap, np.float32)
+        ts, txy = np.zeros(cap, np.uint64), np.zeros((cap, 2), np.int32)
+        nc, ns = C.c_int32(), C.c_int32()
+        out = _MatchOut(sl.ctypes.data, sr.ctypes.data, corr.ctypes.data, C.addressof(nc), supp_xy.ctypes.data,
+                        supp_d.ctypes.data, C.addressof(ns), ts.ctypes.data, txy.ctypes.data)
+        rc, mask_l, mask_r = call(C.byref(out))
+        assert rc in (0, 1), "reference harness returned %d" % rc
+        c = np.zeros(nc.value, CORR_DTYPE)
+        for k, name in enumerate(("sx", "sy", "tx", "ty")):
+            c[name] = corr[:nc.value, k]
+        s = np.zeros(ns.value, SUPPORT_DTYPE)
+        s["x"], s["y"], s["d"] = supp_xy[:ns.value, 0], supp_xy[:ns.value, 1], supp_d[:ns.value]
+        nl, nr = len(mask_l), len(mask_r)
+        return RefMatch(rc, mask_l, mask_r, sl[:nl].copy(), sr[:nr].copy(), c, s, ts[:nr].copy(), txy[:nr].copy())
+
+    def match_pair(self, rawL, rawR, forest_path, settings):
+        """readForest -> preprocessImage x2 -> stereoMatch / rectifiedMatch on a raw pair."""
+        rawL, rawR = np.ascontiguousarray(rawL), np.ascontiguousarray(rawR)
+        H, W = rawL.shape
+        ml, mr = np.empty(H * W, np.int32), np.empty(H * W, np.int32)
+        ncand = np.zeros(2, np.int32)
+        s = settings
+
+        def call(out):
+            rc = self.lib.gpc_reff_match_pair(_u8p(rawL), _u8p(rawR), W, H, forest_path.encode(), s.gradient_threshold,
+                                              s.disp_high, s.vertical_tolerance, s.epipolar_mode, s.use_hashtable,
+                                              _i32p(ml), _i32p(mr), _i32p(ncand), out)
+            return rc, ml[:ncand[0]].copy(), mr[:ncand[1]].copy()
+        return self._run(H * W, call)
+
+    def match_pre(self, pl, pr, forest_path, settings):
+        """The same from two (smooth, grad, mask) triples."""
+        pl = (np.ascontiguousarray(pl[0]), np.ascontiguousarray(pl[1]), np.ascontiguousarray(pl[2], np.int32))
+        pr = (np.ascontiguousarray(pr[0]), np.ascontiguousarray(pr[1]), np.ascontiguousarray(pr[2], np.int32))
+        H, W = pl[0].shape
+        s = settings
+
+        def call(out):
+            rc = self.lib.gpc_reff_match_pre(_u8p(pl[0]), _u8p(pl[1]), _i32p(pl[2]), len(pl[2]),
+                                             _u8p(pr[0]), _u8p(pr[1]), _i32p(pr[2]), len(pr[2]), W, H,
+                                             forest_path.encode(), s.gradient_threshold, s.disp_high,
+                                             s.vertical_tolerance, s.epipolar_mode, s.use_hashtable, out)
+            return rc, pl[2], pr[2]
+        return self._run(max(len(pl[2]), len(pr[2]), 1), call)
+
+    def find_correspondences(self, ss, sk, ts, tk):
+        """Forest::findCorrespondences on bare (state, k) sets.  Returns (pairs [n][2] of (source k, target k),
+        sorted target states, sorted target k) -- the sorted arrays are the reference's own."""
+        ss, ts = np.array(ss, np.uint64), np.array(ts, np.uint64)
+        sk, tk = np.array(sk, np.int32), np.array(tk, np.int32)
+        out = np.zeros((max(len(ss), 1), 2), np.int32)
+        n = self.lib.gpc_reff_find_correspondences(_u64p(ss), _i32p(sk), len(ss), _u64p(ts), _i32p(tk), len(ts),
+                                                   _i32p(out))
+        assert n >= 0, "no target descriptor: undefined in the reference"
+        return out[:n].copy(), ts, tk
+
+    @staticmethod
+    def _params(params):
+        p = np.ascontiguousarray(params, SPLIT_DTYPE)
+        flat = np.empty((len(p), 3), np.int32)
+        flat[:, 0], flat[:, 1], flat[:, 2] = p["i"], p["j"], p["tau"]
+        return flat
+
+    def eval_split(self, triplets, marks, params, score_until_level, w1):
+        t = np.ascontiguousarray(triplets, np.uint8)
+        m = np.ascontiguousarray(marks, np.uint8)
+        p = self._params(params)
+        d, i = np.zeros(4, np.float64), np.zeros(4, np.int32)
+        self.lib.gpc_reff_eval_split(_u8p(t), _u8p(m), len(t), _i32p(p), len(p), C.c_int(score_until_level),
+                                     C.c_double(w1), d.ctypes.data_as(C.c_void_p), _i32p(i))
+        out = np.zeros(1, STATS_DTYPE)
+        out["prec"], out["rec"], out["hmean"], out["convcomb"] = d
+        out["tp"], out["fp"], out["fn"], out["tot"] = i
+        return out[0]
+
+    def mark_split_samples(self, triplets, marks, params, num_params):
+        t = np.ascontiguousarray(triplets, np.uint8)
+        p = self._params(params)
+        assert marks.dtype == np.uint8 and marks.flags.c_contiguous
+        self.lib.gpc_reff_mark_split_samples(_u8p(t), _u8p(marks), len(t), _i32p(p), C.c_int(num_params))
+
+    def get_decisions(self, triplet, i, j, tau):
+        t = np.ascontiguousarray(triplet, np.uint8)
+        assert t.size == 3 * PATCH
+        out = np.zeros(3, np.uint8)
+        self.lib.gpc_reff_get_decisions(_u8p(t), int(i), int(j), int(tau), _u8p(out))
+        return out.astype(bool)
+
+    def disparity_vis(self, img, supp):
+        """getDisparityVisualization(image, supports) as an (H, W, 3) RGB byte array."""
+        img = np.ascontiguousarray(img, np.uint8)
+        H, W = img.shape
+        xy = np.empty((len(supp), 2), np.int32)
+        xy[:, 0], xy[:, 1] = supp["x"], supp["y"]
+        d = np.ascontiguousarray(supp["d"], np.float32)
+        rgb = np.zeros((H, W, 3), np.uint8)
+        rc = self.lib.gpc_reff_disparity_vis(_u8p(img), W, H, _i32p(xy), d.ctypes.data_as(C.c_void_p), len(supp),
+                                             _u8p(rgb))
+        assert rc == 0, rc
+        return rgb

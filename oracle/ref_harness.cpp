@@ -9,9 +9,9 @@
 // filter.hpp includes "gpc/buffer.hpp" only for its transitive std headers; that
 // header needs Eigen, which this image does not have, so the build passes
 // -D__NDB_BUFFER (buffer.hpp's own include guard, buffer.hpp:31) which makes the
-// include expand to nothing.  No stand-in header is written.  inference.hpp /
-// buffer.hpp themselves (Forest, Buffer<T>) cannot be built here (Eigen) -- the
-// API-level behaviour is pinned by SURVEY.md Appendix C instead.
+// include expand to nothing; this translation unit needs no stand-in header.
+// inference.hpp / buffer.hpp themselves (Forest, Buffer<T>) are built by
+// ref_full_harness.cpp, against the container stand-in of oracle/eigen_standin.
 //
 // Build: see oracle/Makefile (target _ref/libgpc_ref.so).
 #include <algorithm>

@@ -1,8 +1,8 @@
 """Fern training scoring loop: Fern::evalSplit / markSplitSamples / train.
 
-PARITY UNPINNED: the reference holds no tests or vectors for training and Fern.hpp / Feature.hpp
-cannot be compiled in this image (Eigen), so the C oracle (oracle/gpc_oracle_train.c) is checked
-here against an independent numpy restatement of the same reference lines, and the HIP path is
+The C oracle (oracle/gpc_oracle_train.c) is checked here against an independent numpy restatement of
+the same reference lines (and in tests/test_oracle_vs_ref_full.py against the reference's own
+Fern::evalSplit / markSplitSamples / Feature::getDecisions), and the HIP path is
 checked against the oracle (bit-exact counts and parameters; the double statistics are the same
 expressions evaluated in the same order, compared exactly)."""
 import numpy as np
