@@ -42,6 +42,10 @@
 using namespace std;  // the reference's headers do this; callers rely on it (sparsematch.cpp)
 
 namespace gpc {
+namespace evaluation {  // gpc/evaluation.hpp (extension: matches scored against ground truth)
+class Truth;
+struct Score;
+}  // namespace evaluation
 namespace inference {
 
 typedef std::chrono::high_resolution_clock::time_point time_point;
@@ -256,6 +260,17 @@ class Forest {
     if (candidatesR) *candidatesR = cr;
     return supp;
   }
+  // Extension (gpc/evaluation.hpp, which defines these): matchPair / sequenceMatch with the records scored against ground
+  // truth on the device instead of returned (gpc_hip_score_batch / gpc_hip_score_sequence); precision and recall counts
+  // per pair.  A failed call returns a zero Score / an empty vector (lastStatus() says why).
+  evaluation::Score scorePair(ndb::Buffer<uint8_t>& simg, ndb::Buffer<uint8_t>& timg, FilterMask& forestmask,
+                              InferenceSettings settings, const evaluation::Truth& truth, const std::vector<float>& thresholds);
+  evaluation::Score scorePair(ndb::Buffer<uint8_t>& simg, ndb::Buffer<uint8_t>& timg, std::vector<FilterMask>& groups,
+                              InferenceSettings settings, const evaluation::Truth& truth, const std::vector<float>& thresholds);
+  std::vector<evaluation::Score> scoreSequence(std::vector<ndb::Buffer<uint8_t>>& frames, FilterMask& fm,
+                                               InferenceSettings settings, const std::vector<evaluation::Truth>& truths,
+                                               const std::vector<float>& thresholds);
+
   // the warm-up of readForest for a group-mode forest (gpc_hip_warmup with the groups set)
   void warmUp(std::vector<FilterMask>& groups) {
     detail::ContextHolder& h = detail::holder(true);
@@ -453,6 +468,8 @@ class Forest {
   }
 
  private:
+  evaluation::Score scoreWith(detail::ContextHolder& h, ndb::Buffer<uint8_t>& simg, ndb::Buffer<uint8_t>& timg,
+                              InferenceSettings settings, const evaluation::Truth& truth, const std::vector<float>& thresholds);
   // What the reference's caller does next -- preprocessImage x2, rectifiedMatch / matchPair on images of this size --
   // done once here on a synthetic image and thrown away: context, code objects, workspaces and page-locked staging
   // (gpc_hip_warmup), and this thread's own staging and the allocator's state for result arrays of this size (the dry run

@@ -421,6 +421,87 @@ int gpc_hip_extract_triplets_device(gpc_hip_ctx* ctx, const uint8_t* d_rawL, con
  * the byte order of Feature::storeAllTriplets (Feature.hpp:254-263).  Synchronous. */
 int gpc_hip_train_set_read(gpc_hip_ctx* ctx, gpc_hip_train_set* set, int first, int n, uint8_t* aos);
 
+/* ---- scoring against ground truth ------------------------------------------------ */
+/* How good a result is, as exact counts per pair: the share of the records that lie within a few pixels of ground truth
+ * (precision = n_within[k] / n_judged) and the share of the matchable pixels that were found (recall = n_within[k] /
+ * n_matchable) -- the pair of figures the Global Patch Collider is evaluated by and Fern.hpp's trainer optimises.  Records,
+ * candidate images and truth stay in HBM; a handful of integers per pair come back.  The library returns counts only. */
+#define GPC_SCORE_MAX_THR 8
+typedef struct gpc_truth {          /* device pointers (host pointers in the host forms), one entry per pair */
+  const float*   u;                 /* [P][H][W]  stereo: disparity g >= 0, true right x = x - g.  flow: du    */
+  const float*   v;                 /* [P][H][W]  flow: dv.  Must be NULL for supports                          */
+  const uint8_t* ignore;            /* [P][H][W]  nonzero = do not judge this source pixel.  May be NULL        */
+} gpc_truth;
+typedef struct gpc_score {          /* one per pair; every field an exact count */
+  int64_t n_records;                /* records looked at: min(count, cap)                                       */
+  int64_t n_ignored;                /* source pixel set in `ignore`                                             */
+  int64_t n_no_truth;               /* not ignored, truth not finite or |u| or |v| >= 1e9 (.flo "unknown")      */
+  int64_t n_judged;                 /* the rest: n_records == n_ignored + n_no_truth + n_judged                 */
+  int64_t n_within[GPC_SCORE_MAX_THR]; /* judged records with e2 <= thr[k]^2; entries >= n_thr are 0            */
+  int64_t sum_e2_q8;                /* sum over judged records of (int64)(min(e2, 1048576.f) * 256.f + 0.5f);    */
+                                    /* min is fminf: an e2 that is NaN or +inf contributes the clamp, 2^28       */
+  int64_t n_candidates;             /* match-and-score forms: candidates of the left image (frame t); else 0    */
+  int64_t n_matchable;              /* match-and-score forms: see below; else 0                                 */
+} gpc_score;
+/* The error of a record, in float32 with one rounding per operation (no fused multiply-add):
+ *   correspondence (sx, sy, tx, ty), truth (u, v) read at (sx, sy):
+ *     ex = float(tx - sx) - u; ey = float(ty - sy) - v; e2 = fl(fl(ex * ex) + fl(ey * ey));
+ *   support (x, y, d), truth g read at (x, y): ex = d - g; e2 = fl(ex * ex);
+ *   n_within[k] counts e2 <= fl(thr[k] * thr[k]).
+ * A judged record whose own values make e2 NaN or +inf (a support with d = NaN or +-inf) stays judged, is within no
+ * threshold, and adds the clamp to sum_e2_q8.
+ * thr: n_thr floats, 1 <= n_thr <= GPC_SCORE_MAX_THR, each finite and >= 0 (GPC_E_INVALID otherwise).  A record whose
+ * source pixel lies outside the image is invalid input; nothing is read for it and it counts as n_no_truth.
+ * n_matchable counts the left candidates (x, y) that are not ignored, whose truth is usable, whose true target --
+ * (x - R(g), y) for stereo, (x + R(u), y + R(v)) for flow, R = roundf, half away from zero -- lies inside the candidate
+ * margin [13, W-13) x [13, H-13) and is itself a candidate of the right image (frame t + 1).  A candidate is what
+ * gpc_hip_preprocess lists: gradient set, inside the margin.
+ *
+ * Records the caller already holds on the device, in the layout gpc_hip_match_batch_device / gpc_hip_match_sequence_device
+ * write them: d_records[npairs][cap_per_pair], d_counts[npairs] true counts (may exceed cap_per_pair: min(count, cap) are
+ * read).  Pure functions of their arguments: no forest is needed, d_counts is read on the device, and the calls only queue
+ * work on the context's stream (read d_scores[npairs], which they overwrite, after gpc_hip_synchronize or another wait on
+ * the stream).  Supports take truth->v == NULL, correspondences need truth->v. */
+int gpc_hip_score_supports_device(gpc_hip_ctx* ctx, const gpc_support* d_supports, int cap_per_pair, const int32_t* d_counts,
+                                  int width, int height, int npairs, const gpc_truth* truth, const float* thr, int n_thr,
+                                  gpc_score* d_scores);
+int gpc_hip_score_correspondences_device(gpc_hip_ctx* ctx, const gpc_correspondence* d_corr, int cap_per_pair,
+                                         const int32_t* d_counts, int width, int height, int npairs, const gpc_truth* truth,
+                                         const float* thr, int n_thr, gpc_score* d_scores);
+/* Match and score: gpc_hip_match_batch_device with the records kept in a workspace of the context that holds every record
+ * of every pair ((width - 26) * (height - 26) + 1 per pair, n_groups times that in group mode), then scored; n_candidates
+ * and n_matchable are filled from the candidate images the pipeline left on the device.  Every setting and arithmetic
+ * gpc_hip_match_batch_device takes is taken, group mode with the sort matchers included, and what it refuses is refused
+ * with the same status.  Waiting is as for gpc_hip_match_batch_device.  With two lanes (gpc_hip_set_pipeline(ctx, 2)) the
+ * lanes are drained and the call runs on the context's stream.
+ * Alignment: the matchable pass reads four pixels of a plane at a time, so truth->u (and truth->v) must be 16-byte
+ * aligned and truth->ignore 4-byte aligned (GPC_E_INVALID otherwise; width % 16 == 0 keeps every pair's plane aligned).
+ * The records forms above have no such requirement. */
+int gpc_hip_score_batch_device(gpc_hip_ctx* ctx, const uint8_t* d_rawL, const uint8_t* d_rawR, int width, int height,
+                               int npairs, const gpc_settings* settings, const gpc_truth* truth, const float* thr, int n_thr,
+                               gpc_score* d_scores);
+/* The same over gpc_hip_match_sequence_device: pair t is frames t and t + 1, truth and d_scores have nframes - 1 entries,
+ * correspondences are scored (truth->v is needed).  Group mode: GPC_E_UNSUPPORTED, as for the sequence itself. */
+int gpc_hip_score_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int width, int height, int nframes,
+                                  const gpc_settings* settings, const gpc_truth* truth, const float* thr, int n_thr,
+                                  gpc_score* d_scores);
+/* Host records [npairs][cap_per_pair], host counts, host truth and host scores through the records forms; synchronous, in
+ * chunks of at most 16 pairs through the context's page-locked arena where the arrays are pageable.  No forest needed. */
+int gpc_hip_score_supports(gpc_hip_ctx* ctx, const gpc_support* supports, int cap_per_pair, const int32_t* counts, int width,
+                           int height, int npairs, const gpc_truth* truth, const float* thr, int n_thr, gpc_score* scores);
+int gpc_hip_score_correspondences(gpc_hip_ctx* ctx, const gpc_correspondence* corr, int cap_per_pair, const int32_t* counts,
+                                  int width, int height, int npairs, const gpc_truth* truth, const float* thr, int n_thr,
+                                  gpc_score* scores);
+/* Host images, host truth, host scores; synchronous.  The pairs (frames) pass through the device forms in chunks of at
+ * most 16 -- truth is 8 to 9 bytes per pixel -- through the context's page-locked arena where the arrays are pageable (a
+ * _begin call still pending on the context is waited for and ended, as gpc_hip_match_sequence does); consecutive chunks
+ * of a sequence share one frame.  The scores equal the device forms' byte for byte. */
+int gpc_hip_score_batch(gpc_hip_ctx* ctx, const uint8_t* rawL, const uint8_t* rawR, int width, int height, int npairs,
+                        const gpc_settings* settings, const gpc_truth* truth, const float* thr, int n_thr, gpc_score* scores);
+int gpc_hip_score_sequence(gpc_hip_ctx* ctx, const uint8_t* frames, int width, int height, int nframes,
+                           const gpc_settings* settings, const gpc_truth* truth, const float* thr, int n_thr,
+                           gpc_score* scores);
+
 /* ---- measurement -------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the context's stream.  When enabled every launch of
  * the named kernels is bracketed by hipEvents; gpc_hip_kernel_time returns the summed

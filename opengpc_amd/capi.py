@@ -22,6 +22,11 @@ OK, E_INVALID, E_NO_DEVICE, E_HIP, E_CAPACITY, E_NO_FOREST, E_FOREST_RANGE, E_IO
 
 SUPPORT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("d", "<f4")])
 CORR_DTYPE = np.dtype([("src_x", "<i4"), ("src_y", "<i4"), ("tar_x", "<i4"), ("tar_y", "<i4")])
+SCORE_MAX_THR = 8   # GPC_SCORE_MAX_THR
+# gpc_score: exact counts per pair
+SCORE_DTYPE = np.dtype([("n_records", "<i8"), ("n_ignored", "<i8"), ("n_no_truth", "<i8"), ("n_judged", "<i8"),
+                        ("n_within", "<i8", (SCORE_MAX_THR,)), ("sum_e2_q8", "<i8"), ("n_candidates", "<i8"),
+                        ("n_matchable", "<i8")])
 
 
 class Settings(C.Structure):
@@ -44,6 +49,11 @@ class Settings(C.Structure):
     def sparsematch(cls):
         """The settings of samples/sparsematch.cpp:29-34."""
         return cls(5, 128, 0, True, False, 1)
+
+
+class Truth(C.Structure):
+    """gpc_truth: u / v / ignore planes, one [H][W] entry per pair (device pointers, or host pointers in the host forms)."""
+    _fields_ = [("u", C.c_void_p), ("v", C.c_void_p), ("ignore", C.c_void_p)]
 
 
 class FilterMask(C.Structure):
@@ -85,6 +95,9 @@ SYMBOLS = [
     "gpc_hip_train_begin_fern", "gpc_hip_train_eval_level", "gpc_hip_train_commit_level",
     "gpc_hip_extract_triplets", "gpc_hip_extract_triplets_device", "gpc_hip_train_set_read",
     "gpc_hip_match_sequence_device", "gpc_hip_match_sequence",
+    "gpc_hip_score_supports_device", "gpc_hip_score_correspondences_device", "gpc_hip_score_batch_device",
+    "gpc_hip_score_sequence_device", "gpc_hip_score_batch", "gpc_hip_score_sequence",
+    "gpc_hip_score_supports", "gpc_hip_score_correspondences",
 ]
 
 
@@ -145,6 +158,18 @@ def load():
     L.gpc_hip_match_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings),
                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.gpc_hip_match_sequence.argtypes = L.gpc_hip_match_sequence_device.argtypes
+    rec = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Truth), C.c_void_p, C.c_int,
+           C.c_void_p]
+    L.gpc_hip_score_supports_device.argtypes = rec
+    L.gpc_hip_score_correspondences_device.argtypes = rec
+    L.gpc_hip_score_supports.argtypes = rec
+    L.gpc_hip_score_correspondences.argtypes = rec
+    L.gpc_hip_score_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings),
+                                             C.POINTER(Truth), C.c_void_p, C.c_int, C.c_void_p]
+    L.gpc_hip_score_batch.argtypes = L.gpc_hip_score_batch_device.argtypes
+    L.gpc_hip_score_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings),
+                                                C.POINTER(Truth), C.c_void_p, C.c_int, C.c_void_p]
+    L.gpc_hip_score_sequence.argtypes = L.gpc_hip_score_sequence_device.argtypes
     L.gpc_hip_match_batch_device_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(Settings), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                     C.c_void_p]
@@ -286,6 +311,38 @@ def _host_frames(a):
     if a.dtype != np.uint8:
         raise ValueError("rawL / rawR: uint8 frames (got %s)" % a.dtype)
     return np.ascontiguousarray(a)
+
+
+def score_thresholds(thr):
+    """thresholds as the float32 array the library takes: 1 .. 8 values, each finite and >= 0 (ValueError otherwise)"""
+    t = np.ascontiguousarray(np.atleast_1d(np.asarray(thr, np.float32)))
+    if t.ndim != 1 or not 1 <= len(t) <= SCORE_MAX_THR:
+        raise ValueError("thresholds: between 1 and %d values" % SCORE_MAX_THR)
+    if not np.isfinite(t).all() or (t < 0).any():
+        raise ValueError("thresholds: finite and >= 0")
+    return t
+
+
+def _host_truth(u, v, ignore, shape, flow):
+    """host truth planes of `shape` = (P, H, W) as contiguous arrays (float32 u, v; uint8 ignore); supports take no v"""
+    if flow and v is None:
+        raise ValueError("truth: correspondences need v")
+    if not flow and v is not None:
+        raise ValueError("truth: v must be None for supports")
+    out = []
+    for name, a, dt in (("u", u, np.float32), ("v", v, np.float32), ("ignore", ignore, np.uint8)):
+        if a is None:
+            if name == "u":
+                raise ValueError("truth: u is needed")
+            out.append(None)
+            continue
+        a = np.asarray(a)
+        if a.dtype != dt:
+            raise ValueError("truth %s: %s planes (got %s)" % (name, np.dtype(dt).name, a.dtype))
+        if a.shape != tuple(shape):
+            raise ValueError("truth %s: shape %s, expected %s" % (name, a.shape, tuple(shape)))
+        out.append(np.ascontiguousarray(a))
+    return out
 
 
 _live_contexts = weakref.WeakSet()
@@ -580,6 +637,104 @@ class Context:
         self._ck(self.L.gpc_hip_match_sequence_device(self.h, C.c_void_p(d_frames), width, height, nframes,
                                                       C.byref(settings), C.c_void_p(d_out), cap_per_pair,
                                                       C.c_void_p(d_counts), C.c_void_p(d_ncand or 0)))
+
+    # ---- scoring against ground truth (gpc_hip_score_*): exact counts per pair, SCORE_DTYPE
+    def _score_records_device(self, fn, d_records, cap_per_pair, d_counts, width, height, npairs, d_u, d_v, d_ignore,
+                              thr, d_scores, flow):
+        t = score_thresholds(thr)
+        if not d_records or not d_counts or not d_scores or not d_u:
+            raise ValueError("records, counts, scores and truth u: device pointers")
+        if flow and not d_v:
+            raise ValueError("truth: correspondences need v")
+        if not flow and d_v:
+            raise ValueError("truth: v must be 0 for supports")
+        if int(cap_per_pair) <= 0 or int(npairs) <= 0 or int(width) <= 0 or int(height) <= 0:
+            raise ValueError("cap_per_pair, npairs, width, height: positive")
+        tr = Truth(d_u, d_v or None, d_ignore or None)
+        self._ck(fn(self.h, C.c_void_p(d_records), int(cap_per_pair), C.c_void_p(d_counts), int(width), int(height),
+                    int(npairs), C.byref(tr), _ptr(t), len(t), C.c_void_p(d_scores)))
+
+    def score_supports_device(self, d_supports, cap_per_pair, d_counts, width, height, npairs, d_u, d_ignore, thr, d_scores):
+        """Supports [npairs][cap_per_pair] already in HBM against disparity truth d_u [npairs][H][W] (float32) and an
+        optional ignore mask (uint8) -> d_scores[npairs] (SCORE_DTYPE), asynchronous.  Pointers are integers."""
+        self._score_records_device(self.L.gpc_hip_score_supports_device, d_supports, cap_per_pair, d_counts, width, height,
+                                   npairs, d_u, 0, d_ignore, thr, d_scores, False)
+
+    def score_correspondences_device(self, d_corr, cap_per_pair, d_counts, width, height, npairs, d_u, d_v, d_ignore, thr,
+                                     d_scores):
+        """Correspondences [npairs][cap_per_pair] in HBM against flow truth (d_u, d_v) -> d_scores[npairs]."""
+        self._score_records_device(self.L.gpc_hip_score_correspondences_device, d_corr, cap_per_pair, d_counts, width,
+                                   height, npairs, d_u, d_v, d_ignore, thr, d_scores, True)
+
+    def score_batch_device(self, d_rawL, d_rawR, width, height, npairs, settings, d_u, d_ignore, thr, d_scores):
+        """match_batch_device + scoring without the records leaving the library: d_scores[npairs], n_candidates and
+        n_matchable filled."""
+        t = score_thresholds(thr)
+        if not d_rawL or not d_rawR or not d_u or not d_scores or int(npairs) <= 0:
+            raise ValueError("images, truth u and scores: device pointers; npairs positive")
+        tr = Truth(d_u, None, d_ignore or None)
+        self._ck(self.L.gpc_hip_score_batch_device(self.h, C.c_void_p(d_rawL), C.c_void_p(d_rawR), int(width), int(height),
+                                                   int(npairs), C.byref(settings), C.byref(tr), _ptr(t), len(t),
+                                                   C.c_void_p(d_scores)))
+
+    def score_sequence_device(self, d_frames, width, height, nframes, settings, d_u, d_v, d_ignore, thr, d_scores):
+        """match_sequence_device + scoring: truth planes and d_scores have nframes - 1 entries."""
+        t = score_thresholds(thr)
+        if not d_frames or not d_u or not d_v or not d_scores or int(nframes) < 2:
+            raise ValueError("frames, truth u, v and scores: device pointers; at least two frames")
+        tr = Truth(d_u, d_v, d_ignore or None)
+        self._ck(self.L.gpc_hip_score_sequence_device(self.h, C.c_void_p(d_frames), int(width), int(height), int(nframes),
+                                                      C.byref(settings), C.byref(tr), _ptr(t), len(t), C.c_void_p(d_scores)))
+
+    def score_records(self, records, counts, u, v, ignore, thr):
+        """Host records [P, cap] (SUPPORT_DTYPE with v None, CORR_DTYPE with flow truth) and their true counts [P] against
+        host truth planes [P, H, W] -> SCORE_DTYPE [P] (gpc_hip_score_supports / gpc_hip_score_correspondences)."""
+        t = score_thresholds(thr)
+        records = np.asarray(records)
+        if records.dtype not in (SUPPORT_DTYPE, CORR_DTYPE) or records.ndim != 2 or records.shape[1] < 1:
+            raise ValueError("records: [P, cap] of SUPPORT_DTYPE or CORR_DTYPE")
+        flow = records.dtype == CORR_DTYPE
+        records = np.ascontiguousarray(records)
+        counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+        P, cap = records.shape
+        uu = np.asarray(u) if u is not None else None
+        if uu is None or uu.ndim != 3 or uu.shape[0] != P or len(counts) != P:
+            raise ValueError("counts [P] and truth planes [P, H, W] for P = %d pairs" % P)
+        u, v, ignore = _host_truth(u, v, ignore, uu.shape, flow)
+        scores = np.zeros(P, SCORE_DTYPE)
+        tr = Truth(u.ctypes.data, v.ctypes.data if flow else None, ignore.ctypes.data if ignore is not None else None)
+        fn = self.L.gpc_hip_score_correspondences if flow else self.L.gpc_hip_score_supports
+        self._ck(fn(self.h, _ptr(records), cap, _ptr(counts), uu.shape[2], uu.shape[1], P, C.byref(tr), _ptr(t), len(t),
+                    _ptr(scores)))
+        return scores
+
+    def score_batch(self, rawL, rawR, settings, u, ignore, thr):
+        """Host pairs [P, H, W] and host truth (u float32 [P, H, W], ignore uint8 [P, H, W] or None) -> SCORE_DTYPE [P]."""
+        t = score_thresholds(thr)
+        rawL, rawR = _host_frames(rawL), _host_frames(rawR)
+        if rawL.ndim != 3 or rawL.shape != rawR.shape:
+            raise ValueError("rawL / rawR: (P, H, W) arrays of one shape")
+        P, H, W = rawL.shape
+        u, _, ignore = _host_truth(u, None, ignore, rawL.shape, False)
+        scores = np.zeros(P, SCORE_DTYPE)
+        tr = Truth(u.ctypes.data, None, ignore.ctypes.data if ignore is not None else None)
+        self._ck(self.L.gpc_hip_score_batch(self.h, _ptr(rawL), _ptr(rawR), W, H, P, C.byref(settings), C.byref(tr), _ptr(t),
+                                            len(t), _ptr(scores)))
+        return scores
+
+    def score_sequence(self, frames, settings, u, v, ignore, thr):
+        """Host frames [N, H, W] and host flow truth of the N - 1 consecutive pairs -> SCORE_DTYPE [N - 1]."""
+        t = score_thresholds(thr)
+        frames = _host_frames(frames)
+        if frames.ndim != 3 or frames.shape[0] < 2:
+            raise ValueError("frames: (N, H, W) with N >= 2")
+        N, H, W = frames.shape
+        u, v, ignore = _host_truth(u, v, ignore, (N - 1, H, W), True)
+        scores = np.zeros(N - 1, SCORE_DTYPE)
+        tr = Truth(u.ctypes.data, v.ctypes.data, ignore.ctypes.data if ignore is not None else None)
+        self._ck(self.L.gpc_hip_score_sequence(self.h, _ptr(frames), W, H, N, C.byref(settings), C.byref(tr), _ptr(t), len(t),
+                                               _ptr(scores)))
+        return scores
 
     # ---- fern training: the scoring loop
     def train_set(self, triplets):

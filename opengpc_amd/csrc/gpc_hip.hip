@@ -36,6 +36,7 @@
 #include "k_rowjoin.h"
 #include "k_rowjoin_fused.h"
 #include "k_rows.h"
+#include "k_score.h"
 #include "k_train.h"
 #include "k_union.h"
 
@@ -52,11 +53,14 @@ enum KernelId {
   KID_GLOBAL_MATCH,
   KID_TRAIN_EVAL,
   KID_GROUP_UNION,
+  KID_SCORE_RECORDS,
+  KID_SCORE_MATCHABLE,
   KID_COUNT
 };
 const char* const kKernelNames[KID_COUNT] = {
     "k_preprocess", "k_hash", "k_row_join", "k_gather_rows",
-    "k_mask", "k_global_keys", "k_global_sort", "k_global_match", "k_train_eval", "k_group_union"};
+    "k_mask", "k_global_keys", "k_global_sort", "k_global_match", "k_train_eval", "k_group_union",
+    "k_score_records", "k_score_matchable"};
 
 struct DevBuf {
   void* p = nullptr;
@@ -233,6 +237,9 @@ struct gpc_hip_ctx {
   bool gtau = false;           // one of the groups has a nonzero tau
   DevBuf gforest_dev;          // [3][GPC_MAX_GROUPS] GpcForestDev: SSE order, Naive order, SSE with the tall tile's offsets
   DevBuf vstats, vcand, vout, vcnt, vncand, uplane, ublk, gdense;  // virtual-pair statistics / candidates / results, union state
+  // scoring (gpc_hip_score_*): every record of every pair of a match-and-score call and their counts; the host forms' chunk
+  // of images and truth, and its scores
+  DevBuf sc_rec, sc_cnt, sc_in, sc_out;
   DevBuf sstats;  // frame sequences: the frames' statistics expanded into the pair layout [npairs*2] (k_seq_stats)
 
   // workspaces
@@ -2106,7 +2113,7 @@ int gpc_hip_destroy(gpc_hip_ctx* c) {
                     &c->gvals[0], &c->gvals[1], &c->ghist, &c->gmisc, &c->hkeys[0], &c->hkeys[1],
                     &c->hvals[0], &c->hvals[1], &c->hrec, &c->forest_dev, &c->packed, &c->gpart, &c->jstate, &c->gkv,
                     &c->res_smooth, &c->res_grad, &c->ext_raw, &c->ext_smooth, &c->ext_grad, &c->ext_groups,
-                    &c->sstats};
+                    &c->sstats, &c->sc_rec, &c->sc_cnt, &c->sc_in, &c->sc_out};
   while (!c->train_sets.empty()) (void)gpc_hip_train_set_destroy(c, c->train_sets.back());
   for (DevBuf* b : bufs) release(*b);
   for (auto& s : c->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -3259,6 +3266,330 @@ int gpc_hip_match_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, 
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (ncand) memcpy(ncand, hn, sizeof(int32_t) * nframes);
   return status;
+}
+
+// ------------------------------------------------------------------ scoring against ground truth
+
+static_assert(sizeof(gpc_score) == sizeof(gpc::ScoreDev), "gpc_score and the kernels' view of it");
+static_assert(GPC_SCORE_MAX_THR == SC_MAX_THR, "threshold slots");
+
+// fl(thr * thr) per threshold, -1 beyond n_thr; GPC_E_INVALID for a count outside 1 .. 8 or a threshold that is negative or not finite
+static int score_thresholds(const float* thr, int n_thr, gpc::ScoreThr& t) {
+  if (!thr || n_thr < 1 || n_thr > GPC_SCORE_MAX_THR) return GPC_E_INVALID;
+  for (int k = 0; k < GPC_SCORE_MAX_THR; ++k) {
+    if (k >= n_thr) {
+      t.t2[k] = -1.f;
+      continue;
+    }
+    const volatile float v = thr[k];
+    if (!(v >= 0.f) || !(v <= 3.402823466e38f)) return GPC_E_INVALID;
+    const volatile float sq = v * v;  // (one float32 rounding, whatever the host compiler's excess precision)
+    t.t2[k] = sq;
+  }
+  return GPC_OK;
+}
+
+static int truth_ok(const gpc_truth* truth, bool corr) {
+  if (!truth || !truth->u) return GPC_E_INVALID;
+  if (corr ? !truth->v : truth->v != nullptr) return GPC_E_INVALID;
+  return GPC_OK;
+}
+
+// k_score_matchable reads four pixels of a truth plane with one 16-byte load and four ignore bytes with one 4-byte load
+static int truth_aligned(const gpc_truth* truth) {
+  if (((uintptr_t)truth->u & 15u) || ((uintptr_t)truth->v & 15u) || ((uintptr_t)truth->ignore & 3u)) return GPC_E_INVALID;
+  return GPC_OK;
+}
+
+// d_scores is cleared on the stream, then the records kernel runs over d_rec[npairs][cap]
+static int score_records(gpc_hip_ctx* c, const void* d_rec, bool corr, long cap, const int32_t* d_counts, int W, int H,
+                         int npairs, const gpc_truth* truth, const gpc::ScoreThr& t, gpc_score* d_scores) {
+  HIPCHK(c, hipMemsetAsync(d_scores, 0, sizeof(gpc_score) * (size_t)npairs, c->stream));
+  const long nchunk = (cap + SC_CHUNK - 1) / SC_CHUNK;
+  const dim3 grid((unsigned)(nchunk < 1024 ? nchunk : 1024), npairs);
+  Timed tm(c, KID_SCORE_RECORDS);
+  snprintf(c->launch_name[KID_SCORE_RECORDS], sizeof c->launch_name[0], "gpc::k_score_records<%s>", corr ? "true" : "false");
+  if (corr)
+    hipLaunchKernelGGL((gpc::k_score_records<true>), grid, dim3(SC_THREADS), 0, c->stream, (const gpc::ScRec<true>*)d_rec, cap,
+                       d_counts, W, H, truth->u, truth->v, truth->ignore, t, (gpc::ScoreDev*)d_scores);
+  else
+    hipLaunchKernelGGL((gpc::k_score_records<false>), grid, dim3(SC_THREADS), 0, c->stream, (const gpc::ScRec<false>*)d_rec, cap,
+                       d_counts, W, H, truth->u, (const float*)nullptr, truth->ignore, t, (gpc::ScoreDev*)d_scores);
+  HIPCHK(c, hipGetLastError());
+  return GPC_OK;
+}
+
+// n_candidates / n_matchable from the gradient images the pipeline just left in c->grad (bit or byte form)
+static int score_matchable(gpc_hip_ctx* c, bool flow, int lstride, int W, int H, int npairs, const gpc_truth* truth,
+                           gpc_score* d_scores) {
+  const long groups = (long)(H - 2 * GPC_R) * W / SC_PX;
+  const long nblk = (groups + SC_THREADS - 1) / SC_THREADS;
+  const dim3 grid((unsigned)(nblk < 256 ? nblk : 256), npairs);
+  const GpcDivW dw = make_divw(W);
+  const bool bits = c->grad_is_bits;
+  Timed tm(c, KID_SCORE_MATCHABLE);
+  snprintf(c->launch_name[KID_SCORE_MATCHABLE], sizeof c->launch_name[0], "gpc::k_score_matchable<%s, %s>", flow ? "true" : "false",
+           bits ? "true" : "false");
+#define LAUNCH_MATCHABLE(FLOW, BITS)                                                                                          \
+  hipLaunchKernelGGL((gpc::k_score_matchable<FLOW, BITS>), grid, dim3(SC_THREADS), 0, c->stream, (const uint8_t*)c->grad.p, \
+                     lstride, W, H, dw, truth->u, truth->v, truth->ignore, (gpc::ScoreDev*)d_scores)
+  if (flow) {
+    if (bits) LAUNCH_MATCHABLE(true, true); else LAUNCH_MATCHABLE(true, false);
+  } else {
+    if (bits) LAUNCH_MATCHABLE(false, true); else LAUNCH_MATCHABLE(false, false);
+  }
+#undef LAUNCH_MATCHABLE
+  HIPCHK(c, hipGetLastError());
+  return GPC_OK;
+}
+
+static int score_records_entry(gpc_hip_ctx* c, const void* d_rec, bool corr, int cap, const int32_t* d_counts, int W, int H,
+                               int npairs, const gpc_truth* truth, const float* thr, int n_thr, gpc_score* d_scores) {
+  if (!c || !d_rec || !d_counts || !d_scores || npairs <= 0 || cap <= 0 || W <= 0 || H <= 0) return GPC_E_INVALID;
+  if ((long)W * H > (1l << 30)) return GPC_E_UNSUPPORTED;
+  CHK(truth_ok(truth, corr));
+  gpc::ScoreThr t;
+  CHK(score_thresholds(thr, n_thr, t));
+  HIPCHK(c, hipSetDevice(c->device));
+  return score_records(c, d_rec, corr, cap, d_counts, W, H, npairs, truth, t, d_scores);
+}
+
+int gpc_hip_score_supports_device(gpc_hip_ctx* c, const gpc_support* d_supports, int cap_per_pair, const int32_t* d_counts, int W,
+                                  int H, int npairs, const gpc_truth* truth, const float* thr, int n_thr, gpc_score* d_scores) {
+  return score_records_entry(c, d_supports, false, cap_per_pair, d_counts, W, H, npairs, truth, thr, n_thr, d_scores);
+}
+
+int gpc_hip_score_correspondences_device(gpc_hip_ctx* c, const gpc_correspondence* d_corr, int cap_per_pair,
+                                         const int32_t* d_counts, int W, int H, int npairs, const gpc_truth* truth,
+                                         const float* thr, int n_thr, gpc_score* d_scores) {
+  return score_records_entry(c, d_corr, true, cap_per_pair, d_counts, W, H, npairs, truth, thr, n_thr, d_scores);
+}
+
+// lanes = 1 for the duration of a match-and-score call: it runs on the context itself
+namespace {
+struct StrictScope {
+  gpc_hip_ctx* c;
+  int lanes;
+  explicit StrictScope(gpc_hip_ctx* ctx) : c(ctx), lanes(ctx->pipeline) { c->pipeline = 1; }
+  ~StrictScope() { c->pipeline = lanes; }
+};
+}  // namespace
+
+int gpc_hip_score_batch_device(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H, int npairs,
+                               const gpc_settings* s, const gpc_truth* truth, const float* thr, int n_thr, gpc_score* d_scores) {
+  if (!c || !d_rawL || !d_rawR || !d_scores || npairs <= 0) return GPC_E_INVALID;
+  CHK(truth_ok(truth, false));
+  CHK(truth_aligned(truth));
+  gpc::ScoreThr t;
+  CHK(score_thresholds(thr, n_thr, t));
+  CHK(check_settings(s));
+  CHK(check_dims(W, H));
+  CHK(forest_matches(c, W, H));
+  const int G = c->ngroups > 1 ? c->ngroups : 1;
+  if (G > 1 && s->use_hashtable) return GPC_E_UNSUPPORTED;  // (as gpc_hip_match_batch_device, before any workspace is made)
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->pipeline > 1) CHK(drain_lanes(c));
+  // every record of every pair: a group has at most one record per left candidate, a union at most G
+  const long cap = (long)G * (W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;
+  if (cap > 0x7FFFFFFFl) return GPC_E_UNSUPPORTED;
+  CHK(ensure(c, c->sc_rec, sizeof(gpc_support) * (size_t)cap * npairs));
+  CHK(ensure(c, c->sc_cnt, sizeof(int32_t) * (size_t)npairs));
+  {
+    StrictScope strict(c);
+    CHK(gpc_hip_match_batch_device(c, d_rawL, d_rawR, W, H, npairs, s, (gpc_support*)c->sc_rec.p, (int)cap,
+                                   (int32_t*)c->sc_cnt.p, nullptr));
+  }
+  CHK(score_records(c, c->sc_rec.p, false, cap, (const int32_t*)c->sc_cnt.p, W, H, npairs, truth, t, d_scores));
+  return score_matchable(c, false, 2, W, H, npairs, truth, d_scores);
+}
+
+int gpc_hip_score_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W, int H, int nframes, const gpc_settings* s,
+                                  const gpc_truth* truth, const float* thr, int n_thr, gpc_score* d_scores) {
+  if (!c || !d_frames || !d_scores || nframes < 2) return GPC_E_INVALID;
+  CHK(truth_ok(truth, true));
+  CHK(truth_aligned(truth));
+  gpc::ScoreThr t;
+  CHK(score_thresholds(thr, n_thr, t));
+  CHK(check_settings(s));
+  CHK(check_dims(W, H));
+  CHK(forest_matches(c, W, H));
+  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int npairs = nframes - 1;
+  const long cap = (long)(W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;
+  CHK(ensure(c, c->sc_rec, sizeof(gpc_correspondence) * (size_t)cap * npairs));
+  CHK(ensure(c, c->sc_cnt, sizeof(int32_t) * (size_t)npairs));
+  CHK(gpc_hip_match_sequence_device(c, d_frames, W, H, nframes, s, (gpc_correspondence*)c->sc_rec.p, (int)cap,
+                                    (int32_t*)c->sc_cnt.p, nullptr));
+  CHK(score_records(c, c->sc_rec.p, true, cap, (const int32_t*)c->sc_cnt.p, W, H, npairs, truth, t, d_scores));
+  return score_matchable(c, true, 1, W, H, npairs, truth, d_scores);
+}
+
+// Host forms: chunks of at most 16 pairs (frames) through the device forms.  A chunk's images and truth planes are laid out
+// back to back in c->sc_in; pageable arrays pass through the page-locked arena (host_copy), page-locked ones are read where
+// they lie.  One wait per chunk: the arena and sc_in are reused by the next.
+namespace {
+struct ScorePlane {
+  const uint8_t* src;  // host array of the whole call (null: absent)
+  size_t per_item;     // bytes per pair / frame
+};
+}  // namespace
+
+// items [i0, i0 + cnt[k]) of plane k -> sc_in at dev_off[k]
+static int score_upload(gpc_hip_ctx* c, const ScorePlane* planes, const size_t* first, const size_t* cnt, const size_t* dev_off,
+                        int nplanes) {
+  size_t pageable = 0;
+  for (int k = 0; k < nplanes; ++k)
+    if (planes[k].src && !device_view_of_host(planes[k].src)) pageable += pad16(planes[k].per_item * cnt[k]);
+  uint8_t* d_arena = nullptr;
+  if (pageable) {
+    CHK(xfer_reserve(c, pageable, &d_arena));
+    CHK(ensure_pool(c));
+  }
+  size_t at = 0;
+  for (int k = 0; k < nplanes; ++k) {
+    if (!planes[k].src) continue;
+    const size_t bytes = planes[k].per_item * cnt[k];
+    const uint8_t* src = planes[k].src + planes[k].per_item * first[k];
+    if (!device_view_of_host(planes[k].src)) {
+      host_copy(c, c->h_xfer + at, src, bytes, true);
+      src = c->h_xfer + at;
+      at += pad16(bytes);
+    }
+    host_copy_wait(c);
+    HIPCHK(c, hipMemcpyAsync((uint8_t*)c->sc_in.p + dev_off[k], src, bytes, hipMemcpyHostToDevice, c->stream));
+  }
+  return GPC_OK;
+}
+
+// at least `bytes` of the page-locked counts area (pinned_counts sizes it in pairs: three int32 each)
+static int pinned_bytes(gpc_hip_ctx* c, size_t bytes) { return pinned_counts(c, (int)((bytes + 3 * sizeof(int32_t) - 1) / (3 * sizeof(int32_t)))); }
+
+// a chunk's scores -> the caller's array (through the page-locked counts area: 120 bytes per pair), then the chunk is done
+static int score_download(gpc_hip_ctx* c, gpc_score* scores, int n) {
+  CHK(pinned_bytes(c, sizeof(gpc_score) * (size_t)n));
+  HIPCHK(c, hipMemcpyAsync(c->h_cnt, c->sc_out.p, sizeof(gpc_score) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  memcpy(scores, c->h_cnt, sizeof(gpc_score) * (size_t)n);
+  return check_join_err(c);
+}
+
+static int score_host_begin(gpc_hip_ctx* c) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->pend.active || c->pre_slot >= 0) {  // (a pending _begin may still write the arena: waited for and ended)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->pend.active = false;
+    c->pre_slot = -1;
+  }
+  if (c->pipeline > 1) CHK(drain_lanes(c));
+  return GPC_OK;
+}
+
+// records, counts and truth of at most 16 pairs at a time through the records form
+static int score_records_host(gpc_hip_ctx* c, const void* rec, bool corr, int cap, const int32_t* counts, int W, int H, int npairs,
+                              const gpc_truth* truth, const float* thr, int n_thr, gpc_score* scores) {
+  if (!c || !rec || !counts || !scores || npairs <= 0 || cap <= 0 || W <= 0 || H <= 0) return GPC_E_INVALID;
+  if ((long)W * H > (1l << 30)) return GPC_E_UNSUPPORTED;
+  CHK(truth_ok(truth, corr));
+  gpc::ScoreThr t;
+  CHK(score_thresholds(thr, n_thr, t));
+  CHK(score_host_begin(c));
+  const size_t n = (size_t)W * H, esz = corr ? sizeof(gpc_correspondence) : sizeof(gpc_support);
+  const int K = npairs < 16 ? npairs : 16;
+  size_t off[5];
+  off[0] = 0;
+  off[1] = pad16(esz * (size_t)cap * K);
+  off[2] = off[1] + pad16(sizeof(int32_t) * (size_t)K);
+  off[3] = off[2] + pad16(sizeof(float) * n * K);
+  off[4] = off[3] + (corr ? pad16(sizeof(float) * n * K) : 0);
+  CHK(ensure(c, c->sc_in, off[4] + n * K));
+  CHK(ensure(c, c->sc_out, sizeof(gpc_score) * (size_t)K));
+  const ScorePlane planes[5] = {{(const uint8_t*)rec, esz * (size_t)cap}, {(const uint8_t*)counts, sizeof(int32_t)},
+                                {(const uint8_t*)truth->u, sizeof(float) * n}, {(const uint8_t*)truth->v, sizeof(float) * n},
+                                {truth->ignore, n}};
+  for (int p0 = 0; p0 < npairs; p0 += K) {
+    const int pc = npairs - p0 < K ? npairs - p0 : K;
+    size_t first[5], cnt[5];
+    for (int k = 0; k < 5; ++k) first[k] = (size_t)p0, cnt[k] = (size_t)pc;
+    CHK(score_upload(c, planes, first, cnt, off, 5));
+    const uint8_t* d = (const uint8_t*)c->sc_in.p;
+    const gpc_truth dt = {(const float*)(d + off[2]), corr ? (const float*)(d + off[3]) : nullptr, truth->ignore ? d + off[4] : nullptr};
+    CHK(score_records(c, d + off[0], corr, cap, (const int32_t*)(d + off[1]), W, H, pc, &dt, t, (gpc_score*)c->sc_out.p));
+    CHK(score_download(c, scores + p0, pc));
+  }
+  return GPC_OK;
+}
+
+int gpc_hip_score_supports(gpc_hip_ctx* c, const gpc_support* supports, int cap_per_pair, const int32_t* counts, int W, int H,
+                           int npairs, const gpc_truth* truth, const float* thr, int n_thr, gpc_score* scores) {
+  return score_records_host(c, supports, false, cap_per_pair, counts, W, H, npairs, truth, thr, n_thr, scores);
+}
+
+int gpc_hip_score_correspondences(gpc_hip_ctx* c, const gpc_correspondence* corr, int cap_per_pair, const int32_t* counts, int W,
+                                  int H, int npairs, const gpc_truth* truth, const float* thr, int n_thr, gpc_score* scores) {
+  return score_records_host(c, corr, true, cap_per_pair, counts, W, H, npairs, truth, thr, n_thr, scores);
+}
+
+int gpc_hip_score_batch(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, int W, int H, int npairs, const gpc_settings* s,
+                        const gpc_truth* truth, const float* thr, int n_thr, gpc_score* scores) {
+  if (!c || !rawL || !rawR || !scores || npairs <= 0) return GPC_E_INVALID;
+  CHK(truth_ok(truth, false));
+  gpc::ScoreThr t;
+  CHK(score_thresholds(thr, n_thr, t));
+  CHK(check_settings(s));
+  CHK(check_dims(W, H));
+  CHK(forest_matches(c, W, H));
+  if (c->ngroups > 1 && s->use_hashtable) return GPC_E_UNSUPPORTED;
+  CHK(score_host_begin(c));
+  const size_t n = (size_t)W * H;
+  const int K = npairs < 16 ? npairs : 16;
+  const size_t off[4] = {0, n * K, 2 * n * K, 2 * n * K + sizeof(float) * n * K};
+  CHK(ensure(c, c->sc_in, off[3] + n * K));
+  CHK(ensure(c, c->sc_out, sizeof(gpc_score) * (size_t)K));
+  const ScorePlane planes[4] = {{rawL, n}, {rawR, n}, {(const uint8_t*)truth->u, sizeof(float) * n}, {truth->ignore, n}};
+  for (int p0 = 0; p0 < npairs; p0 += K) {
+    const int pc = npairs - p0 < K ? npairs - p0 : K;
+    const size_t first[4] = {(size_t)p0, (size_t)p0, (size_t)p0, (size_t)p0}, cnt[4] = {(size_t)pc, (size_t)pc, (size_t)pc, (size_t)pc};
+    CHK(score_upload(c, planes, first, cnt, off, 4));
+    const uint8_t* d = (const uint8_t*)c->sc_in.p;
+    const gpc_truth dt = {(const float*)(d + off[2]), nullptr, truth->ignore ? d + off[3] : nullptr};
+    CHK(gpc_hip_score_batch_device(c, d + off[0], d + off[1], W, H, pc, s, &dt, thr, n_thr, (gpc_score*)c->sc_out.p));
+    CHK(score_download(c, scores + p0, pc));
+  }
+  return GPC_OK;
+}
+
+int gpc_hip_score_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, int nframes, const gpc_settings* s,
+                           const gpc_truth* truth, const float* thr, int n_thr, gpc_score* scores) {
+  if (!c || !frames || !scores || nframes < 2) return GPC_E_INVALID;
+  CHK(truth_ok(truth, true));
+  gpc::ScoreThr t;
+  CHK(score_thresholds(thr, n_thr, t));
+  CHK(check_settings(s));
+  CHK(check_dims(W, H));
+  CHK(forest_matches(c, W, H));
+  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
+  CHK(score_host_begin(c));
+  const size_t n = (size_t)W * H;
+  const int npairs = nframes - 1;
+  const int K = c->seq_frames > 1 && c->seq_frames < 16 ? c->seq_frames : 16;  // frames per chunk (GPC_HIP_SEQ_FRAMES: tests)
+  const int kf = nframes < K ? nframes : K, step = kf - 1;                    // (consecutive chunks share a frame)
+  const size_t pl = sizeof(float) * n * (kf - 1);
+  const size_t off[4] = {0, pad16(n * kf), pad16(n * kf) + pl, pad16(n * kf) + 2 * pl};
+  CHK(ensure(c, c->sc_in, off[3] + n * (kf - 1)));
+  CHK(ensure(c, c->sc_out, sizeof(gpc_score) * (size_t)(kf - 1)));
+  const ScorePlane planes[4] = {{frames, n}, {(const uint8_t*)truth->u, sizeof(float) * n}, {(const uint8_t*)truth->v, sizeof(float) * n},
+                                {truth->ignore, n}};
+  for (int p0 = 0; p0 < npairs; p0 += step) {
+    const int pc = npairs - p0 < step ? npairs - p0 : step;
+    const size_t first[4] = {(size_t)p0, (size_t)p0, (size_t)p0, (size_t)p0}, cnt[4] = {(size_t)pc + 1, (size_t)pc, (size_t)pc, (size_t)pc};
+    CHK(score_upload(c, planes, first, cnt, off, 4));
+    const uint8_t* d = (const uint8_t*)c->sc_in.p;
+    const gpc_truth dt = {(const float*)(d + off[1]), (const float*)(d + off[2]), truth->ignore ? d + off[3] : nullptr};
+    CHK(gpc_hip_score_sequence_device(c, d + off[0], W, H, pc + 1, s, &dt, thr, n_thr, (gpc_score*)c->sc_out.p));
+    CHK(score_download(c, scores + p0, pc));
+  }
+  return GPC_OK;
 }
 
 int gpc_hip_match_batch_device_packed(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H,

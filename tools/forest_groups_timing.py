@@ -65,11 +65,16 @@ def case(g, torch, name, W, H, Ls, Rs, Ds, iters):
         kt = {k: round(1e3 * v[0] / v[1], 1) for k, v in ctx.kernel_times().items() if v[1]}
         ctx.enable_kernel_timing(False)
         cnt = d_cnt.cpu().numpy()
-        right = wrong = 0
-        for p in range(B):
-            d = d_out[p, :int(cnt[p]), 2].cpu().numpy().copy().view(np.float32)
-            right += int((d == Ds[p]).sum())
-            wrong += int((d != Ds[p]).sum())
+        # d == D counted on the device: truth D everywhere, threshold 0 (gpc_hip_score_batch_device)
+        d_u = torch.from_numpy(np.stack([np.full((H, W), D, np.float32) for D in Ds])).to(d_out.device)
+        d_sc = torch.zeros((B, 15), dtype=torch.int64, device=d_out.device)
+        torch.cuda.synchronize()
+        ctx.score_batch_device(d_L.data_ptr(), d_R.data_ptr(), W, H, B, s, d_u.data_ptr(), 0, [0.0], d_sc.data_ptr())
+        ctx.synchronize()
+        sc = d_sc.cpu().numpy().view(g.SCORE_DTYPE).reshape(-1)
+        assert int(sc["n_records"].sum()) == int(cnt.sum())
+        right = int(sc["n_within"][:, 0].sum())
+        wrong = int(sc["n_judged"].sum()) - right
         res[mode] = {"us_per_call": round(1e3 * ms, 1), "us_per_pair": round(1e3 * ms / B, 2), "kernels_us": kt,
                      "launch_names": {k: v for k, v in ctx.kernel_launch_names().items() if v},
                      "supports": int(cnt.sum()), "supports_d_eq_D": right, "supports_d_ne_D": wrong}
