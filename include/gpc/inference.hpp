@@ -46,6 +46,9 @@ namespace evaluation {  // gpc/evaluation.hpp (extension: matches scored against
 class Truth;
 struct Score;
 }  // namespace evaluation
+namespace tracking {  // gpc/tracking.hpp (extension: point tracks over a frame sequence)
+struct Track;
+}  // namespace tracking
 namespace inference {
 
 typedef std::chrono::high_resolution_clock::time_point time_point;
@@ -270,6 +273,11 @@ class Forest {
   std::vector<evaluation::Score> scoreSequence(std::vector<ndb::Buffer<uint8_t>>& frames, FilterMask& fm,
                                                InferenceSettings settings, const std::vector<evaluation::Truth>& truths,
                                                const std::vector<float>& thresholds);
+
+  // Extension (gpc/tracking.hpp, which defines it): sequenceMatch with the correspondences of consecutive pairs chained
+  // into point tracks on the device (gpc_hip_track_sequence); the tracks of at least minLength records, in track-id order.
+  std::vector<tracking::Track> trackSequence(std::vector<ndb::Buffer<uint8_t>>& frames, FilterMask& fm,
+                                             InferenceSettings settings, int minLength = 1);
 
   // the warm-up of readForest for a group-mode forest (gpc_hip_warmup with the groups set)
   void warmUp(std::vector<FilterMask>& groups) {

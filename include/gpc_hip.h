@@ -502,6 +502,70 @@ int gpc_hip_score_sequence(gpc_hip_ctx* ctx, const uint8_t* frames, int width, i
                            const gpc_settings* settings, const gpc_truth* truth, const float* thr, int n_thr,
                            gpc_score* scores);
 
+/* ---- point tracks over a frame sequence ------------------------------------------- */
+/* Which match of pair t + 1 continues which match of pair t: the records of gpc_hip_match_sequence[_device] chained into
+ * tracks on the device, so that a video user (structure from motion, stabilisation, long-range evaluation) gets a point's
+ * positions over the frames instead of independent lists in code order.  The reference has no counterpart: it matches
+ * one pair (Forest::stereoMatch, inference.hpp:344-361) and leaves every use of two results to its caller.  The rule is
+ * therefore this library's own; it is made of integers only, so that every implementation of it gives the same bytes.
+ *
+ * Input: P = npairs lists corr[t][0 .. m_t), m_t = min(counts[t], cap_per_pair) (a negative count reads as 0), for frames
+ * of width x height.  A pixel's index is y * width + x.  A record whose source or target lies outside
+ * [0, width) x [0, height) takes no part: it is nobody's successor candidate and has none, so it is a track of length 1.
+ *   Successor candidate of record i of pair t < P - 1: J = the lowest j < m_{t+1} (among the records that take part) whose
+ *     source pixel equals i's target pixel; none if there is no such j.
+ *   Link: among the records of pair t with the same J the lowest i gets next[t][i] = J, the others -1; next[P-1][.] = -1.
+ *     "Lowest" because the matchers emit a pair's records in a fixed order, so the lowest index is the one choice that
+ *     does not depend on which thread arrives first; the sort matchers emit every source and every target pixel at most
+ *     once per pair, so for their records the rule never has to choose -- it matters for the hash-table matcher and for
+ *     records a caller supplies.  Every record has at most one successor and one predecessor: the links form chains.
+ *   Tracks: a head is a record without a predecessor.  Heads are numbered 0, 1, ... by (t ascending, i ascending); that
+ *     number is track_id[t][i] of every record on the head's chain.  Row k of the table describes track k.
+ * next and track_id are [npairs][cap_per_pair] like the records; entries at i >= m_t are left untouched.  *n_tracks is
+ * the true number of tracks; the first min(*n_tracks, track_cap) rows of `tracks` are written (track_cap = 0: `tracks`
+ * may be NULL).  npairs * cap_per_pair must not exceed 2^31 - 1, cap_per_pair and width * height 2^30 and npairs 65535
+ * (GPC_E_UNSUPPORTED). */
+typedef struct gpc_track {
+  int32_t first_pair;   /* the head's pair: the point is seen in frames first_pair .. first_pair + length        */
+  int32_t first_record; /* the head's index in corr[first_pair]                                                 */
+  int32_t length;       /* records on the chain, >= 1                                                           */
+  int32_t last_record;  /* index of the chain's last record, in corr[first_pair + length - 1]                   */
+} gpc_track;
+/* Records already on the device in the layout gpc_hip_match_sequence_device writes.  No forest is needed; d_counts is read
+ * on the device, and the call only queues work on the context's stream (six launches: fill the per-pixel planes, scatter
+ * the record indices, link, settle shared successors and count heads, scan, walk the chains); read the outputs after
+ * gpc_hip_synchronize or another wait on the stream.  Workspaces of the context, grown on demand: 4 bytes per pixel for
+ * each of the pairs 1 .. P-1, 4 bytes per record slot. */
+int gpc_hip_track_records_device(gpc_hip_ctx* ctx, const gpc_correspondence* d_corr, int cap_per_pair, const int32_t* d_counts,
+                                 int width, int height, int npairs, int32_t* d_next, int32_t* d_track_id, gpc_track* d_tracks,
+                                 int track_cap, int32_t* d_ntracks);
+/* gpc_hip_match_sequence_device exactly as it is (every matcher setting, either arithmetic; its outputs d_corr, d_counts,
+ * d_ncand as it documents them, its waiting too), then the links over what it wrote.  Group mode: GPC_E_UNSUPPORTED, as
+ * for the sequence itself; no forest: GPC_E_NO_FOREST. */
+int gpc_hip_track_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int width, int height, int nframes,
+                                  const gpc_settings* settings, gpc_correspondence* d_corr, int cap_per_pair, int32_t* d_counts,
+                                  int32_t* d_ncand, int32_t* d_next, int32_t* d_track_id, gpc_track* d_tracks, int track_cap,
+                                  int32_t* d_ntracks);
+/* The same from / to host memory (pageable or page-locked), synchronous.  GPC_E_CAPACITY when a pair's count exceeds
+ * cap_per_pair or *n_tracks exceeds track_cap; what is written is then as defined above (the first cap_per_pair records of
+ * a pair are the ones linked).  gpc_hip_track_records needs no forest and sends each pair's first m_t records only. */
+int gpc_hip_track_records(gpc_hip_ctx* ctx, const gpc_correspondence* corr, int cap_per_pair, const int32_t* counts, int width,
+                          int height, int npairs, int32_t* next, int32_t* track_id, gpc_track* tracks, int track_cap,
+                          int32_t* n_tracks);
+/* Frames in, records (corr, counts, ncand[nframes] optional: as gpc_hip_match_sequence) and their tracks out.  A track may
+ * run through every frame, so the sequence is not cut into chunks: all of it is staged on the device and the device form
+ * runs once (pageable frames pass through the page-locked arena, as in gpc_hip_match_sequence, with the same effect on a
+ * pending _begin).  The call is therefore BOUNDED BY DEVICE MEMORY: it holds
+ *   nframes * W * H  +  (nframes - 1) * cap_per_pair * 24  +  track_cap * 16   bytes of staging (16 per record slot, 4
+ *   for its link, 4 for its track id; the counts and the padding of each block to 16 bytes are not counted),
+ *   (nframes - 2) * W * H * 4  +  (nframes - 1) * cap_per_pair * 4              bytes of linking workspace (plus 4 bytes
+ *   per 2048 record slots for the head counts), and
+ *   what gpc_hip_match_sequence_device keeps for nframes frames (smoothed image, gradient image and codes: 6 bytes per
+ *   pixel and frame, plus the chosen matcher's own workspaces).  Longer videos: overlapping calls, stitched by the caller. */
+int gpc_hip_track_sequence(gpc_hip_ctx* ctx, const uint8_t* frames, int width, int height, int nframes,
+                           const gpc_settings* settings, gpc_correspondence* corr, int cap_per_pair, int32_t* counts,
+                           int32_t* ncand, int32_t* next, int32_t* track_id, gpc_track* tracks, int track_cap, int32_t* n_tracks);
+
 /* ---- measurement -------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the context's stream.  When enabled every launch of
  * the named kernels is bracketed by hipEvents; gpc_hip_kernel_time returns the summed

@@ -27,6 +27,8 @@ SCORE_MAX_THR = 8   # GPC_SCORE_MAX_THR
 SCORE_DTYPE = np.dtype([("n_records", "<i8"), ("n_ignored", "<i8"), ("n_no_truth", "<i8"), ("n_judged", "<i8"),
                         ("n_within", "<i8", (SCORE_MAX_THR,)), ("sum_e2_q8", "<i8"), ("n_candidates", "<i8"),
                         ("n_matchable", "<i8")])
+# gpc_track: one row per track (gpc_hip_track_*)
+TRACK_DTYPE = np.dtype([("first_pair", "<i4"), ("first_record", "<i4"), ("length", "<i4"), ("last_record", "<i4")])
 
 
 class Settings(C.Structure):
@@ -98,6 +100,7 @@ SYMBOLS = [
     "gpc_hip_score_supports_device", "gpc_hip_score_correspondences_device", "gpc_hip_score_batch_device",
     "gpc_hip_score_sequence_device", "gpc_hip_score_batch", "gpc_hip_score_sequence",
     "gpc_hip_score_supports", "gpc_hip_score_correspondences",
+    "gpc_hip_track_records_device", "gpc_hip_track_sequence_device", "gpc_hip_track_records", "gpc_hip_track_sequence",
 ]
 
 
@@ -170,6 +173,13 @@ def load():
     L.gpc_hip_score_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings),
                                                 C.POINTER(Truth), C.c_void_p, C.c_int, C.c_void_p]
     L.gpc_hip_score_sequence.argtypes = L.gpc_hip_score_sequence_device.argtypes
+    L.gpc_hip_track_records_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.gpc_hip_track_records.argtypes = L.gpc_hip_track_records_device.argtypes
+    L.gpc_hip_track_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_void_p,
+                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_void_p]
+    L.gpc_hip_track_sequence.argtypes = L.gpc_hip_track_sequence_device.argtypes
     L.gpc_hip_match_batch_device_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(Settings), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                     C.c_void_p]
@@ -735,6 +745,71 @@ class Context:
         self._ck(self.L.gpc_hip_score_sequence(self.h, _ptr(frames), W, H, N, C.byref(settings), C.byref(tr), _ptr(t), len(t),
                                                _ptr(scores)))
         return scores
+
+    # ---- point tracks (gpc_hip_track_*): the records of consecutive pairs chained on the device
+    def track_records_device(self, d_corr, cap_per_pair, d_counts, width, height, npairs, d_next, d_track_id, d_tracks,
+                             track_cap, d_ntracks):
+        """Correspondences [npairs][cap_per_pair] already in HBM (the layout match_sequence_device writes) -> d_next and
+        d_track_id [npairs][cap_per_pair] int32, d_tracks [track_cap] of TRACK_DTYPE, d_ntracks [1] int32; asynchronous, no
+        forest needed.  Pointers are integers."""
+        self._ck(self.L.gpc_hip_track_records_device(self.h, C.c_void_p(d_corr), int(cap_per_pair), C.c_void_p(d_counts),
+                                                     int(width), int(height), int(npairs), C.c_void_p(d_next),
+                                                     C.c_void_p(d_track_id), C.c_void_p(d_tracks or 0), int(track_cap),
+                                                     C.c_void_p(d_ntracks)))
+
+    def track_sequence_device(self, d_frames, width, height, nframes, settings, d_corr, cap_per_pair, d_counts, d_ncand,
+                              d_next, d_track_id, d_tracks, track_cap, d_ntracks):
+        """match_sequence_device, then the links over what it wrote (gpc_hip_track_sequence_device)."""
+        self._ck(self.L.gpc_hip_track_sequence_device(self.h, C.c_void_p(d_frames), int(width), int(height), int(nframes),
+                                                      C.byref(settings), C.c_void_p(d_corr), int(cap_per_pair),
+                                                      C.c_void_p(d_counts), C.c_void_p(d_ncand or 0), C.c_void_p(d_next),
+                                                      C.c_void_p(d_track_id), C.c_void_p(d_tracks or 0), int(track_cap),
+                                                      C.c_void_p(d_ntracks)))
+
+    def track_records(self, records, counts, width, height, track_cap=None, next_out=None, id_out=None, tracks_out=None):
+        """Host records [P, cap] of CORR_DTYPE and their true counts [P] -> (next [P, cap] int32, track_id [P, cap] int32,
+        tracks [track_cap] of TRACK_DTYPE, n_tracks, status).  Entries of next / track_id beyond min(counts[t], cap) are
+        left as they were (-1 in arrays made here).  track_cap None: one row per record slot, which always suffices."""
+        records = np.asarray(records)
+        if records.dtype != CORR_DTYPE or records.ndim != 2 or records.shape[1] < 1 or records.shape[0] < 1:
+            raise ValueError("records: [P, cap] of CORR_DTYPE")
+        if not records.flags.c_contiguous:
+            records = np.ascontiguousarray(records)
+        counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+        P, cap = records.shape
+        if len(counts) != P:
+            raise ValueError("counts: one per pair")
+        track_cap = P * cap if track_cap is None else int(track_cap)
+        nxt = next_out if next_out is not None else np.full((P, cap), -1, np.int32)
+        tid = id_out if id_out is not None else np.full((P, cap), -1, np.int32)
+        rows = tracks_out if tracks_out is not None else np.zeros(max(track_cap, 1), TRACK_DTYPE)
+        n = C.c_int32(0)
+        st = self.L.gpc_hip_track_records(self.h, _ptr(records), cap, _ptr(counts), int(width), int(height), P, _ptr(nxt),
+                                          _ptr(tid), _ptr(rows), track_cap, C.byref(n))
+        self._ck(st, allow=(E_CAPACITY,))
+        return nxt, tid, rows[:min(n.value, track_cap)], n.value, st
+
+    def track_sequence(self, frames, settings, cap=None, track_cap=None):
+        """frames: uint8 [N, H, W] in host memory -> (records [N-1, cap], counts [N-1], candidates per frame [N],
+        next [N-1, cap], track_id [N-1, cap], tracks, n_tracks, status): match_sequence plus the tracks of its records.
+        The whole sequence is staged on the device (gpc_hip_track_sequence)."""
+        frames = _host_frames(frames)
+        if frames.ndim != 3 or frames.shape[0] < 2:
+            raise ValueError("frames: (N, H, W) with N >= 2")
+        N, H, W = frames.shape
+        cap = cap if cap is not None else (W - 26) * (H - 26)
+        track_cap = (N - 1) * cap if track_cap is None else int(track_cap)
+        out = np.empty((N - 1, max(cap, 1)), CORR_DTYPE)
+        counts = np.zeros(N - 1, np.int32)
+        ncand = np.zeros(N, np.int32)
+        nxt = np.full((N - 1, max(cap, 1)), -1, np.int32)
+        tid = np.full((N - 1, max(cap, 1)), -1, np.int32)
+        rows = np.zeros(max(track_cap, 1), TRACK_DTYPE)
+        n = C.c_int32(0)
+        st = self.L.gpc_hip_track_sequence(self.h, _ptr(frames), W, H, N, C.byref(settings), _ptr(out), cap, _ptr(counts),
+                                           _ptr(ncand), _ptr(nxt), _ptr(tid), _ptr(rows), track_cap, C.byref(n))
+        self._ck(st, allow=(E_CAPACITY,))
+        return out, counts, ncand, nxt, tid, rows[:min(n.value, track_cap)], n.value, st
 
     # ---- fern training: the scoring loop
     def train_set(self, triplets):

@@ -37,6 +37,7 @@
 #include "k_rowjoin_fused.h"
 #include "k_rows.h"
 #include "k_score.h"
+#include "k_track.h"
 #include "k_train.h"
 #include "k_union.h"
 
@@ -53,6 +54,12 @@ enum KernelId {
   KID_GLOBAL_MATCH,
   KID_TRAIN_EVAL,
   KID_GROUP_UNION,
+  KID_TRACK_FILL,
+  KID_TRACK_SCATTER,
+  KID_TRACK_LINK,
+  KID_TRACK_SETTLE,
+  KID_TRACK_SCAN,
+  KID_TRACK_WALK,
   KID_SCORE_RECORDS,
   KID_SCORE_MATCHABLE,
   KID_COUNT
@@ -60,6 +67,7 @@ enum KernelId {
 const char* const kKernelNames[KID_COUNT] = {
     "k_preprocess", "k_hash", "k_row_join", "k_gather_rows",
     "k_mask", "k_global_keys", "k_global_sort", "k_global_match", "k_train_eval", "k_group_union",
+    "k_track_fill", "k_track_scatter", "k_track_link", "k_track_settle", "k_track_scan", "k_track_walk",
     "k_score_records", "k_score_matchable"};
 
 struct DevBuf {
@@ -240,6 +248,9 @@ struct gpc_hip_ctx {
   // scoring (gpc_hip_score_*): every record of every pair of a match-and-score call and their counts; the host forms' chunk
   // of images and truth, and its scores
   DevBuf sc_rec, sc_cnt, sc_in, sc_out;
+  // point tracks (gpc_hip_track_*): per-pixel planes of pairs 1 .. P-1, predecessor per record, head counts per chunk; the host
+  // forms' staging block (frames or records in, records, links, ids and table out)
+  DevBuf tr_plane, tr_pred, tr_blk, tr_stage;
   DevBuf sstats;  // frame sequences: the frames' statistics expanded into the pair layout [npairs*2] (k_seq_stats)
 
   // workspaces
@@ -2113,7 +2124,8 @@ int gpc_hip_destroy(gpc_hip_ctx* c) {
                     &c->gvals[0], &c->gvals[1], &c->ghist, &c->gmisc, &c->hkeys[0], &c->hkeys[1],
                     &c->hvals[0], &c->hvals[1], &c->hrec, &c->forest_dev, &c->packed, &c->gpart, &c->jstate, &c->gkv,
                     &c->res_smooth, &c->res_grad, &c->ext_raw, &c->ext_smooth, &c->ext_grad, &c->ext_groups,
-                    &c->sstats, &c->sc_rec, &c->sc_cnt, &c->sc_in, &c->sc_out};
+                    &c->sstats, &c->sc_rec, &c->sc_cnt, &c->sc_in, &c->sc_out, &c->tr_plane, &c->tr_pred, &c->tr_blk,
+                    &c->tr_stage};
   while (!c->train_sets.empty()) (void)gpc_hip_train_set_destroy(c, c->train_sets.back());
   for (DevBuf* b : bufs) release(*b);
   for (auto& s : c->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -3590,6 +3602,202 @@ int gpc_hip_score_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, 
     CHK(score_download(c, scores + p0, pc));
   }
   return GPC_OK;
+}
+
+// ------------------------------------------------------------------ point tracks over a frame sequence
+
+static_assert(sizeof(gpc_track) == sizeof(gpc::TrRow) && sizeof(gpc_track) == 16, "gpc_track and the kernels' view of it");
+static_assert(sizeof(gpc_correspondence) == sizeof(gpc::TrRec), "gpc_correspondence and the kernels' view of it");
+
+static int track_args(const gpc_hip_ctx* c, const void* corr, int cap, const void* counts, int W, int H, int npairs,
+                      const void* next, const void* track_id, const void* tracks, int track_cap, const void* ntracks) {
+  if (!c || !corr || !counts || !next || !track_id || !ntracks || npairs < 1 || cap <= 0 || track_cap < 0 || W <= 0 || H <= 0)
+    return GPC_E_INVALID;
+  if (track_cap > 0 && !tracks) return GPC_E_INVALID;
+  // a pixel index takes 30 bits, a record's number in the whole sequence (the largest track id) 31
+  // (and a launch has one grid row per pair); the kernels step a record index in int by up to a grid's width past cap
+  if ((long)W * H > (1l << 30) || (long)npairs * cap > 0x7FFFFFFFl || cap > (1 << 30) || npairs > 65535) return GPC_E_UNSUPPORTED;
+  return GPC_OK;
+}
+
+// The six launches over records already on the device.  The planes are FILLED first (4 bytes per pixel and pair, 16-byte
+// stores): the lowest index of duplicate sources is an integer minimum, and a minimum over whatever an earlier call left
+// in the plane could keep a stale lower index that a later check can only reject, not replace.
+static int track_link(gpc_hip_ctx* c, const gpc_correspondence* d_corr, int cap, const int32_t* d_counts, int W, int H, int P,
+                      int32_t* d_next, int32_t* d_track_id, gpc_track* d_tracks, int track_cap, int32_t* d_ntracks) {
+  const size_t n = (size_t)W * H;
+  const long nchunk = ((long)cap + TR_CHUNK - 1) / TR_CHUNK;
+  const long n16 = (long)((n * (size_t)(P - 1) + 3) / 4);  // (the last group may reach into the slack ensure() leaves)
+  CHK(ensure(c, c->tr_plane, sizeof(int32_t) * n * (size_t)(P - 1)));
+  CHK(ensure(c, c->tr_pred, sizeof(int32_t) * (size_t)cap * P));
+  CHK(ensure(c, c->tr_blk, sizeof(int32_t) * (size_t)nchunk * P));
+  const gpc::TrRec* rec = (const gpc::TrRec*)d_corr;
+  int32_t* plane = (int32_t*)c->tr_plane.p;
+  int32_t* pred = (int32_t*)c->tr_pred.p;
+  int32_t* blk = (int32_t*)c->tr_blk.p;
+  const dim3 sgrid((unsigned)(nchunk < 1024 ? nchunk : 1024), P), cgrid((unsigned)nchunk, P);
+  if (n16 > 0) {
+    const long fb = (n16 + TR_THREADS - 1) / TR_THREADS;
+    Timed t(c, KID_TRACK_FILL);
+    hipLaunchKernelGGL(gpc::k_track_fill, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(TR_THREADS), 0, c->stream, (int4*)plane, n16);
+  }
+  {
+    Timed t(c, KID_TRACK_SCATTER);
+    hipLaunchKernelGGL(gpc::k_track_scatter, sgrid, dim3(TR_THREADS), 0, c->stream, rec, cap, d_counts, W, H, plane, pred);
+  }
+  {
+    Timed t(c, KID_TRACK_LINK);
+    hipLaunchKernelGGL(gpc::k_track_link, sgrid, dim3(TR_THREADS), 0, c->stream, rec, cap, d_counts, W, H, P,
+                       (const int32_t*)plane, pred, d_next);
+  }
+  {
+    Timed t(c, KID_TRACK_SETTLE);
+    hipLaunchKernelGGL(gpc::k_track_settle, cgrid, dim3(TR_THREADS), 0, c->stream, cap, d_counts, P, (const int32_t*)pred, d_next,
+                       blk, (int)nchunk);
+  }
+  {
+    Timed t(c, KID_TRACK_SCAN);
+    hipLaunchKernelGGL(gpc::k_track_scan, dim3(1), dim3(1024), 0, c->stream, blk, nchunk * P, d_ntracks);
+  }
+  {
+    Timed t(c, KID_TRACK_WALK);
+    hipLaunchKernelGGL(gpc::k_track_walk, cgrid, dim3(TR_THREADS), 0, c->stream, cap, d_counts, P, (const int32_t*)pred,
+                       (const int32_t*)d_next, (const int32_t*)blk, (int)nchunk, d_track_id, (gpc::TrRow*)d_tracks, track_cap);
+  }
+  for (int k = KID_TRACK_FILL; k <= KID_TRACK_WALK; ++k) snprintf(c->launch_name[k], sizeof c->launch_name[0], "gpc::%s", kKernelNames[k]);
+  HIPCHK(c, hipGetLastError());
+  return GPC_OK;
+}
+
+int gpc_hip_track_records_device(gpc_hip_ctx* c, const gpc_correspondence* d_corr, int cap_per_pair, const int32_t* d_counts, int W,
+                                 int H, int npairs, int32_t* d_next, int32_t* d_track_id, gpc_track* d_tracks, int track_cap,
+                                 int32_t* d_ntracks) {
+  CHK(track_args(c, d_corr, cap_per_pair, d_counts, W, H, npairs, d_next, d_track_id, d_tracks, track_cap, d_ntracks));
+  HIPCHK(c, hipSetDevice(c->device));
+  return track_link(c, d_corr, cap_per_pair, d_counts, W, H, npairs, d_next, d_track_id, d_tracks, track_cap, d_ntracks);
+}
+
+int gpc_hip_track_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W, int H, int nframes, const gpc_settings* s,
+                                  gpc_correspondence* d_corr, int cap_per_pair, int32_t* d_counts, int32_t* d_ncand,
+                                  int32_t* d_next, int32_t* d_track_id, gpc_track* d_tracks, int track_cap, int32_t* d_ntracks) {
+  if (!c || !d_frames || nframes < 2) return GPC_E_INVALID;
+  CHK(track_args(c, d_corr, cap_per_pair, d_counts, W, H, nframes - 1, d_next, d_track_id, d_tracks, track_cap, d_ntracks));
+  CHK(gpc_hip_match_sequence_device(c, d_frames, W, H, nframes, s, d_corr, cap_per_pair, d_counts, d_ncand));
+  return track_link(c, d_corr, cap_per_pair, d_counts, W, H, nframes - 1, d_next, d_track_id, d_tracks, track_cap, d_ntracks);
+}
+
+// Host forms.  Everything of the call is staged in ONE device block (c->tr_stage) and the device form runs once over it.
+// Pageable input passes through the page-locked arena in pieces of at most 32 MiB, page-locked input is read where it lies.
+static int track_upload(gpc_hip_ctx* c, void* d_dst, const void* src, size_t bytes) {
+  if (!bytes) return GPC_OK;
+  if (device_view_of_host(src)) {
+    HIPCHK(c, hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return GPC_OK;
+  }
+  const size_t piece = (size_t)32 << 20;
+  uint8_t* d_arena = nullptr;
+  CHK(xfer_reserve(c, bytes < piece ? bytes : piece, &d_arena));
+  CHK(ensure_pool(c));
+  for (size_t at = 0; at < bytes; at += piece) {
+    const size_t nb = bytes - at < piece ? bytes - at : piece;
+    host_copy(c, c->h_xfer, (const uint8_t*)src + at, nb, true);
+    host_copy_wait(c);
+    HIPCHK(c, hipMemcpyAsync((uint8_t*)d_dst + at, c->h_xfer, nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (the arena is written again by the next piece)
+  }
+  return GPC_OK;
+}
+
+namespace {
+struct TrackStage {  // offsets into c->tr_stage
+  size_t in, corr, counts, ncand, next, id, tracks, ntracks, bytes;
+};
+TrackStage track_stage(size_t in_bytes, int P, int cap, int track_cap) {
+  TrackStage o;
+  const size_t rec = (size_t)P * cap;
+  o.in = 0;
+  o.corr = pad16(in_bytes);
+  o.counts = o.corr + sizeof(gpc_correspondence) * rec;
+  o.ncand = o.counts + pad16(sizeof(int32_t) * (size_t)P);
+  o.next = o.ncand + pad16(sizeof(int32_t) * (size_t)(P + 1));
+  o.id = o.next + pad16(sizeof(int32_t) * rec);
+  o.tracks = o.id + pad16(sizeof(int32_t) * rec);
+  o.ntracks = o.tracks + sizeof(gpc_track) * (size_t)track_cap;
+  o.bytes = o.ntracks + 16;
+  return o;
+}
+}  // namespace
+
+// counts (and candidate counts) first, then what they say is valid: m_t records, links and ids per pair, min(n, track_cap) rows
+static int track_download(gpc_hip_ctx* c, const TrackStage& o, int P, int cap, int track_cap, gpc_correspondence* corr,
+                          int32_t* counts, int32_t* ncand, int32_t* next, int32_t* track_id, gpc_track* tracks, int32_t* ntracks) {
+  const uint8_t* d = (const uint8_t*)c->tr_stage.p;
+  CHK(pinned_counts(c, P + 2));  // (3 words per pair: counts [P], candidates [P + 1], the number of tracks)
+  int32_t* hc = c->h_cnt;
+  HIPCHK(c, hipMemcpyAsync(hc, d + o.counts, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, c->stream));
+  if (ncand) HIPCHK(c, hipMemcpyAsync(hc + P, d + o.ncand, sizeof(int32_t) * (size_t)(P + 1), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hc + 2 * P + 1, d + o.ntracks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int status = GPC_OK;
+  for (int t = 0; t < P; ++t) {
+    const int m = hc[t] < 0 ? 0 : (hc[t] > cap ? cap : hc[t]);
+    if (hc[t] > cap) status = GPC_E_CAPACITY;
+    if (!m) continue;
+    const size_t at = (size_t)t * cap;
+    if (corr) HIPCHK(c, hipMemcpyAsync(corr + at, d + o.corr + sizeof(gpc_correspondence) * at, sizeof(gpc_correspondence) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(next + at, d + o.next + sizeof(int32_t) * at, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(track_id + at, d + o.id + sizeof(int32_t) * at, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+  }
+  const int n = hc[2 * P + 1];
+  if (n > track_cap) status = GPC_E_CAPACITY;
+  const int rows = n < track_cap ? n : track_cap;
+  if (rows > 0) HIPCHK(c, hipMemcpyAsync(tracks, d + o.tracks, sizeof(gpc_track) * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (counts) memcpy(counts, hc, sizeof(int32_t) * (size_t)P);
+  if (ncand) memcpy(ncand, hc + P, sizeof(int32_t) * (size_t)(P + 1));
+  *ntracks = n;
+  CHK(check_join_err(c));
+  return status;
+}
+
+int gpc_hip_track_records(gpc_hip_ctx* c, const gpc_correspondence* corr, int cap, const int32_t* counts, int W, int H, int npairs,
+                          int32_t* next, int32_t* track_id, gpc_track* tracks, int track_cap, int32_t* ntracks) {
+  CHK(track_args(c, corr, cap, counts, W, H, npairs, next, track_id, tracks, track_cap, ntracks));
+  CHK(score_host_begin(c));
+  const TrackStage o = track_stage(0, npairs, cap, track_cap);
+  CHK(ensure(c, c->tr_stage, o.bytes));
+  uint8_t* d = (uint8_t*)c->tr_stage.p;
+  CHK(track_upload(c, d + o.counts, counts, sizeof(int32_t) * (size_t)npairs));
+  for (int t = 0; t < npairs; ++t) {  // (what lies beyond a pair's count is never read, so it does not travel)
+    const int m = counts[t] < 0 ? 0 : (counts[t] > cap ? cap : counts[t]);
+    const size_t at = sizeof(gpc_correspondence) * (size_t)t * cap;
+    CHK(track_upload(c, d + o.corr + at, corr + (size_t)t * cap, sizeof(gpc_correspondence) * (size_t)m));
+  }
+  CHK(track_link(c, (const gpc_correspondence*)(d + o.corr), cap, (const int32_t*)(d + o.counts), W, H, npairs,
+                 (int32_t*)(d + o.next), (int32_t*)(d + o.id), (gpc_track*)(d + o.tracks), track_cap, (int32_t*)(d + o.ntracks)));
+  return track_download(c, o, npairs, cap, track_cap, nullptr, nullptr, nullptr, next, track_id, tracks, ntracks);
+}
+
+int gpc_hip_track_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, int nframes, const gpc_settings* s,
+                           gpc_correspondence* corr, int cap, int32_t* counts, int32_t* ncand, int32_t* next, int32_t* track_id,
+                           gpc_track* tracks, int track_cap, int32_t* ntracks) {
+  if (!c || !frames || nframes < 2) return GPC_E_INVALID;
+  const int npairs = nframes - 1;
+  CHK(track_args(c, corr, cap, counts, W, H, npairs, next, track_id, tracks, track_cap, ntracks));
+  CHK(check_settings(s));
+  CHK(check_dims(W, H));
+  CHK(forest_matches(c, W, H));
+  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
+  CHK(score_host_begin(c));
+  const size_t n = (size_t)W * H;
+  const TrackStage o = track_stage(n * nframes, npairs, cap, track_cap);
+  CHK(ensure(c, c->tr_stage, o.bytes));
+  uint8_t* d = (uint8_t*)c->tr_stage.p;
+  CHK(track_upload(c, d + o.in, frames, n * nframes));
+  CHK(gpc_hip_track_sequence_device(c, d + o.in, W, H, nframes, s, (gpc_correspondence*)(d + o.corr), cap, (int32_t*)(d + o.counts),
+                                    (int32_t*)(d + o.ncand), (int32_t*)(d + o.next), (int32_t*)(d + o.id),
+                                    (gpc_track*)(d + o.tracks), track_cap, (int32_t*)(d + o.ntracks)));
+  return track_download(c, o, npairs, cap, track_cap, corr, counts, ncand, next, track_id, tracks, ntracks);
 }
 
 int gpc_hip_match_batch_device_packed(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H,
