@@ -566,6 +566,82 @@ int gpc_hip_track_sequence(gpc_hip_ctx* ctx, const uint8_t* frames, int width, i
                            const gpc_settings* settings, gpc_correspondence* corr, int cap_per_pair, int32_t* counts,
                            int32_t* ncand, int32_t* next, int32_t* track_id, gpc_track* tracks, int track_cap, int32_t* n_tracks);
 
+/* ---- match filtering: grid motion consensus ---------------------------------------- */
+/* Rejects the matches their neighbours do not agree with: grid-based motion statistics (GMS, Bian et al., CVPR 2017) -- a
+ * true match is surrounded by matches that move the same way, a false one is not.  The matchers emit every unique-code
+ * collision; this is the filter a user of a sparse matcher applies next, and its output is again a record list in the
+ * library's layout, so gpc_hip_score_*_device and gpc_hip_track_records_device take it unchanged.  The reference has no
+ * counterpart (it matches one pair and leaves the rest to its caller): the rule is this library's own, and it is made of
+ * integers only, so that every implementation of it gives the same bytes.
+ *
+ * Input: P = npairs lists rec[t][0 .. m_t), m_t = min(max(counts[t], 0), cap_per_pair), for images of width x height.
+ *   Source and target: (src_x, src_y) -> (tar_x, tar_y) of a correspondence; (x, y) -> (x - (int)d, y) of a support.
+ *   A record PARTICIPATES iff source and target lie in [0, width) x [0, height); a support must also have d finite,
+ *     d == truncf(d) and |d| < 2^24.  A record that does not participate has keep mask 0 and is counted nowhere.
+ *   Grid s in {0, 1, 2, 3} has the offset (ox, oy) = (0, 0), (c/2, 0), (0, c/2), (c/2, c/2), c = cell; shifts = 1 uses
+ *     grid 0 only.  The cell of a point is ((x + ox) div c, (y + oy) div c); the grid has gx = (width - 1 + ox) div c + 1
+ *     columns and gy = (height - 1 + oy) div c + 1 rows.  The displacement class of a record under grid s is the integer
+ *     vector D = cell(target) - cell(source).
+ *   For record i with source cell A under grid s, over the participating records j of the same pair:
+ *     T_i = the number of j whose source cell lies within Chebyshev distance 1 of A;
+ *     S_i = the number of those with D_j == D_i (i itself included);
+ *     k_i = the number of grid cells within Chebyshev distance 1 of A (9 inside, fewer at the border, 1 in a 1x1 grid).
+ *   i passes under grid s iff S_i * S_i * k_i * alpha_den^2 > alpha_num^2 * T_i (unsigned 64-bit, strict): GMS's
+ *     S > alpha * sqrt(T / k) without the square root.
+ * Output: keep[t][i] (uint8) has bit s set for every grid i passes under; a record is kept iff keep != 0.  The kept
+ * records go to out[t][0 ..] in input order, index[t][n] is the input index of the n-th kept record, out_counts[t] the true
+ * number kept; the first min(out_counts[t], cap_out) entries are written.  Entries of keep at i >= m_t and of out / index
+ * beyond what is written are left untouched.  keep and index may be NULL.
+ * GPC_E_UNSUPPORTED: cap_per_pair > 2^23 (what keeps the products exact: 2^46 * 9 * 2^12 < 2^63),
+ * ceil(width / c) * ceil(height / c) > 2^22, npairs > 65535, npairs * cap_per_pair > 2^31 - 1.  GPC_E_INVALID: parameters
+ * out of range, null required pointers, npairs < 1, cap_per_pair or cap_out < 1, `out` overlapping the input records.
+ * The documented defaults are cell 16, shifts 4, alpha 6 / 1 (GMS's alpha and its shifted grids). */
+typedef struct gpc_consensus {
+  int32_t cell;       /* cell edge in pixels: even, 4 <= cell <= 256                         */
+  int32_t shifts;     /* 1 or 4: grids tried                                                  */
+  int32_t alpha_num;  /* 0 <= alpha_num <= 1024                                               */
+  int32_t alpha_den;  /* 1 <= alpha_den <= 64;  threshold factor alpha = alpha_num/alpha_den  */
+} gpc_consensus;
+/* Records already on the device, in the layout the matchers write: d_rec[npairs][cap_per_pair], d_counts[npairs] (read on
+ * the device), d_keep[npairs][cap_per_pair], d_out and d_index [npairs][cap_out], d_out_counts[npairs].  Pure functions
+ * of their arguments: no forest is needed, and the calls only queue work on the context's stream (per grid: histogram of
+ * the source cells, scan, counting sort, count and test; then chunk counts, scan, ordered write); read the outputs after
+ * gpc_hip_synchronize or another wait on the stream.  Workspaces of the context, grown on demand: 8 bytes per record slot
+ * (9 without d_keep), 8 bytes per pair and grid cell. */
+int gpc_hip_consensus_supports_device(gpc_hip_ctx* ctx, const gpc_support* d_rec, int cap_per_pair, const int32_t* d_counts,
+                                      int width, int height, int npairs, const gpc_consensus* prm, uint8_t* d_keep,
+                                      gpc_support* d_out, int cap_out, int32_t* d_index, int32_t* d_out_counts);
+int gpc_hip_consensus_correspondences_device(gpc_hip_ctx* ctx, const gpc_correspondence* d_rec, int cap_per_pair,
+                                             const int32_t* d_counts, int width, int height, int npairs,
+                                             const gpc_consensus* prm, uint8_t* d_keep, gpc_correspondence* d_out, int cap_out,
+                                             int32_t* d_index, int32_t* d_out_counts);
+/* Match and filter: gpc_hip_match_batch_device / gpc_hip_match_sequence_device exactly as they are, into the workspace
+ * of the context that holds every record of every pair (the one gpc_hip_score_batch_device uses), then the filter over
+ * it.  Settings, refusals, statuses and waiting are those of the match they wrap; with two lanes
+ * (gpc_hip_set_pipeline(ctx, 2)) the lanes are drained and the call runs on the context's stream.  d_raw_counts[P]
+ * (optional) receives the unfiltered counts, d_ncand (optional) the candidate counts as the match writes them ([P][2] for
+ * the batch, [nframes] for the sequence).  Group mode: the batch form filters the union; the sequence form is
+ * GPC_E_UNSUPPORTED, as the sequence itself.  The limits above apply with cap_per_pair = that workspace's capacity,
+ * n_groups * (width - 26) * (height - 26) + 1: a call whose every-record capacity exceeds 2^23 (an image of more than
+ * about 8.3 million inner pixels, or a group-mode forest on a large one) is GPC_E_UNSUPPORTED here although the match
+ * alone would run -- match into an array of the caller's and use the records form with the capacity it needs. */
+int gpc_hip_consensus_batch_device(gpc_hip_ctx* ctx, const uint8_t* d_rawL, const uint8_t* d_rawR, int width, int height,
+                                   int npairs, const gpc_settings* settings, const gpc_consensus* prm, gpc_support* d_out,
+                                   int cap_out, int32_t* d_out_counts, int32_t* d_raw_counts, int32_t* d_ncand);
+int gpc_hip_consensus_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int width, int height, int nframes,
+                                      const gpc_settings* settings, const gpc_consensus* prm, gpc_correspondence* d_out,
+                                      int cap_out, int32_t* d_out_counts, int32_t* d_raw_counts, int32_t* d_ncand);
+/* Host records, counts and outputs through the records forms; synchronous, in chunks of at most 16 pairs, pageable arrays
+ * through the context's page-locked arena.  Each pair's first m_t records travel; what comes back equals the device forms
+ * byte for byte, untouched entries included.  GPC_E_CAPACITY when a pair's kept count exceeds cap_out (out_counts holds
+ * the true counts, the first cap_out kept records of such a pair are delivered). */
+int gpc_hip_consensus_supports(gpc_hip_ctx* ctx, const gpc_support* rec, int cap_per_pair, const int32_t* counts, int width,
+                               int height, int npairs, const gpc_consensus* prm, uint8_t* keep, gpc_support* out, int cap_out,
+                               int32_t* index, int32_t* out_counts);
+int gpc_hip_consensus_correspondences(gpc_hip_ctx* ctx, const gpc_correspondence* rec, int cap_per_pair, const int32_t* counts,
+                                      int width, int height, int npairs, const gpc_consensus* prm, uint8_t* keep,
+                                      gpc_correspondence* out, int cap_out, int32_t* index, int32_t* out_counts);
+
 /* ---- measurement -------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the context's stream.  When enabled every launch of
  * the named kernels is bracketed by hipEvents; gpc_hip_kernel_time returns the summed

@@ -58,6 +58,14 @@ class Truth(C.Structure):
     _fields_ = [("u", C.c_void_p), ("v", C.c_void_p), ("ignore", C.c_void_p)]
 
 
+class Consensus(C.Structure):
+    """gpc_consensus: the parameters of the grid motion consensus filter (gpc_hip_consensus_*); the documented defaults."""
+    _fields_ = [("cell", C.c_int32), ("shifts", C.c_int32), ("alpha_num", C.c_int32), ("alpha_den", C.c_int32)]
+
+    def __init__(self, cell=16, shifts=4, alpha_num=6, alpha_den=1):
+        super().__init__(int(cell), int(shifts), int(alpha_num), int(alpha_den))
+
+
 class FilterMask(C.Structure):
     """gpc::inference::Forest::FilterMask (reference inference.hpp:137-156)."""
     _fields_ = [
@@ -101,6 +109,8 @@ SYMBOLS = [
     "gpc_hip_score_sequence_device", "gpc_hip_score_batch", "gpc_hip_score_sequence",
     "gpc_hip_score_supports", "gpc_hip_score_correspondences",
     "gpc_hip_track_records_device", "gpc_hip_track_sequence_device", "gpc_hip_track_records", "gpc_hip_track_sequence",
+    "gpc_hip_consensus_supports_device", "gpc_hip_consensus_correspondences_device", "gpc_hip_consensus_batch_device",
+    "gpc_hip_consensus_sequence_device", "gpc_hip_consensus_supports", "gpc_hip_consensus_correspondences",
 ]
 
 
@@ -180,6 +190,15 @@ def load():
                                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_void_p]
     L.gpc_hip_track_sequence.argtypes = L.gpc_hip_track_sequence_device.argtypes
+    L.gpc_hip_consensus_supports_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                    C.POINTER(Consensus), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.gpc_hip_consensus_correspondences_device.argtypes = L.gpc_hip_consensus_supports_device.argtypes
+    L.gpc_hip_consensus_supports.argtypes = L.gpc_hip_consensus_supports_device.argtypes
+    L.gpc_hip_consensus_correspondences.argtypes = L.gpc_hip_consensus_supports_device.argtypes
+    L.gpc_hip_consensus_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings),
+                                                 C.POINTER(Consensus), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_consensus_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings),
+                                                    C.POINTER(Consensus), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gpc_hip_match_batch_device_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(Settings), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                     C.c_void_p]
@@ -810,6 +829,59 @@ class Context:
                                            _ptr(ncand), _ptr(nxt), _ptr(tid), _ptr(rows), track_cap, C.byref(n))
         self._ck(st, allow=(E_CAPACITY,))
         return out, counts, ncand, nxt, tid, rows[:min(n.value, track_cap)], n.value, st
+
+    # ---- match filtering (gpc_hip_consensus_*): grid motion consensus over a pair's records
+    def consensus_records_device(self, d_rec, corr, cap_per_pair, d_counts, width, height, npairs, prm, d_keep, d_out, cap_out,
+                                 d_index, d_out_counts):
+        """Records [npairs][cap_per_pair] already in HBM (corr: CORR_DTYPE, else SUPPORT_DTYPE) -> d_keep [npairs][cap_per_pair]
+        uint8 (optional), d_out [npairs][cap_out] kept records in input order, d_index [npairs][cap_out] int32 (optional),
+        d_out_counts [npairs] int32; asynchronous, no forest needed.  Pointers are integers."""
+        fn = self.L.gpc_hip_consensus_correspondences_device if corr else self.L.gpc_hip_consensus_supports_device
+        self._ck(fn(self.h, C.c_void_p(d_rec), int(cap_per_pair), C.c_void_p(d_counts), int(width), int(height), int(npairs),
+                    C.byref(prm), C.c_void_p(d_keep or 0), C.c_void_p(d_out), int(cap_out), C.c_void_p(d_index or 0),
+                    C.c_void_p(d_out_counts)))
+
+    def consensus_batch_device(self, d_rawL, d_rawR, width, height, npairs, settings, prm, d_out, cap_out, d_out_counts,
+                               d_raw_counts=0, d_ncand=0):
+        """match_batch_device into the context's every-record workspace, then the filter: d_out [npairs][cap_out] supports."""
+        self._ck(self.L.gpc_hip_consensus_batch_device(self.h, C.c_void_p(d_rawL), C.c_void_p(d_rawR), int(width), int(height),
+                                                       int(npairs), C.byref(settings), C.byref(prm), C.c_void_p(d_out),
+                                                       int(cap_out), C.c_void_p(d_out_counts), C.c_void_p(d_raw_counts or 0),
+                                                       C.c_void_p(d_ncand or 0)))
+
+    def consensus_sequence_device(self, d_frames, width, height, nframes, settings, prm, d_out, cap_out, d_out_counts,
+                                  d_raw_counts=0, d_ncand=0):
+        """match_sequence_device, then the filter: d_out [nframes-1][cap_out] correspondences."""
+        self._ck(self.L.gpc_hip_consensus_sequence_device(self.h, C.c_void_p(d_frames), int(width), int(height), int(nframes),
+                                                          C.byref(settings), C.byref(prm), C.c_void_p(d_out), int(cap_out),
+                                                          C.c_void_p(d_out_counts), C.c_void_p(d_raw_counts or 0),
+                                                          C.c_void_p(d_ncand or 0)))
+
+    def consensus_records(self, records, counts, width, height, prm=None, cap_out=None, keep=None, out=None, index=None):
+        """Host records [P, cap] (SUPPORT_DTYPE or CORR_DTYPE) and their true counts [P] -> (keep [P, cap] uint8, out
+        [P, cap_out], index [P, cap_out] int32, out_counts [P], status).  Entries the filter does not write are left as
+        they were (0 / -1 in arrays made here); status is E_CAPACITY when a pair keeps more than cap_out records."""
+        records = np.asarray(records)
+        if records.dtype not in (SUPPORT_DTYPE, CORR_DTYPE) or records.ndim != 2 or records.shape[1] < 1 or records.shape[0] < 1:
+            raise ValueError("records: [P, cap] of SUPPORT_DTYPE or CORR_DTYPE")
+        corr = records.dtype == CORR_DTYPE
+        if not records.flags.c_contiguous:
+            records = np.ascontiguousarray(records)
+        counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+        P, cap = records.shape
+        if len(counts) != P:
+            raise ValueError("counts: one per pair")
+        prm = prm if prm is not None else Consensus()
+        cap_out = cap if cap_out is None else int(cap_out)
+        keep = keep if keep is not None else np.zeros((P, cap), np.uint8)
+        out = out if out is not None else np.zeros((P, max(cap_out, 1)), records.dtype)
+        index = index if index is not None else np.full((P, max(cap_out, 1)), -1, np.int32)
+        out_counts = np.zeros(P, np.int32)
+        fn = self.L.gpc_hip_consensus_correspondences if corr else self.L.gpc_hip_consensus_supports
+        st = fn(self.h, _ptr(records), cap, _ptr(counts), int(width), int(height), P, C.byref(prm), _ptr(keep), _ptr(out), cap_out,
+                _ptr(index), _ptr(out_counts))
+        self._ck(st, allow=(E_CAPACITY,))
+        return keep, out, index, out_counts, st
 
     # ---- fern training: the scoring loop
     def train_set(self, triplets):

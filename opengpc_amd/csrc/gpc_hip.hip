@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "gpc_device.h"
+#include "k_consensus.h"
 #include "k_extract.h"
 #include "k_global.h"
 #include "k_hash.h"
@@ -60,6 +61,12 @@ enum KernelId {
   KID_TRACK_SETTLE,
   KID_TRACK_SCAN,
   KID_TRACK_WALK,
+  KID_CONS_CELLS,
+  KID_CONS_SCAN,
+  KID_CONS_SCATTER,
+  KID_CONS_COUNT,
+  KID_CONS_BLOCKS,
+  KID_CONS_WRITE,
   KID_SCORE_RECORDS,
   KID_SCORE_MATCHABLE,
   KID_COUNT
@@ -68,6 +75,7 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_preprocess", "k_hash", "k_row_join", "k_gather_rows",
     "k_mask", "k_global_keys", "k_global_sort", "k_global_match", "k_train_eval", "k_group_union",
     "k_track_fill", "k_track_scatter", "k_track_link", "k_track_settle", "k_track_scan", "k_track_walk",
+    "k_cons_cells", "k_cons_scan", "k_cons_scatter", "k_cons_count", "k_cons_blocks", "k_cons_write",
     "k_score_records", "k_score_matchable"};
 
 struct DevBuf {
@@ -251,6 +259,9 @@ struct gpc_hip_ctx {
   // point tracks (gpc_hip_track_*): per-pixel planes of pairs 1 .. P-1, predecessor per record, head counts per chunk; the host
   // forms' staging block (frames or records in, records, links, ids and table out)
   DevBuf tr_plane, tr_pred, tr_blk, tr_stage;
+  // match filtering (gpc_hip_consensus_*): class and record index per sorted position, cursors and first positions per pair
+  // and grid cell, kept records per chunk, the keep mask where the caller wants none; the host forms' staging block
+  DevBuf cs_key, cs_idx, cs_cur, cs_start, cs_blk, cs_keep, cs_stage;
   DevBuf sstats;  // frame sequences: the frames' statistics expanded into the pair layout [npairs*2] (k_seq_stats)
 
   // workspaces
@@ -2125,7 +2136,7 @@ int gpc_hip_destroy(gpc_hip_ctx* c) {
                     &c->hvals[0], &c->hvals[1], &c->hrec, &c->forest_dev, &c->packed, &c->gpart, &c->jstate, &c->gkv,
                     &c->res_smooth, &c->res_grad, &c->ext_raw, &c->ext_smooth, &c->ext_grad, &c->ext_groups,
                     &c->sstats, &c->sc_rec, &c->sc_cnt, &c->sc_in, &c->sc_out, &c->tr_plane, &c->tr_pred, &c->tr_blk,
-                    &c->tr_stage};
+                    &c->tr_stage, &c->cs_key, &c->cs_idx, &c->cs_cur, &c->cs_start, &c->cs_blk, &c->cs_keep, &c->cs_stage};
   while (!c->train_sets.empty()) (void)gpc_hip_train_set_destroy(c, c->train_sets.back());
   for (DevBuf* b : bufs) release(*b);
   for (auto& s : c->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -3798,6 +3809,264 @@ int gpc_hip_track_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, 
                                     (int32_t*)(d + o.ncand), (int32_t*)(d + o.next), (int32_t*)(d + o.id),
                                     (gpc_track*)(d + o.tracks), track_cap, (int32_t*)(d + o.ntracks)));
   return track_download(c, o, npairs, cap, track_cap, corr, counts, ncand, next, track_id, tracks, ntracks);
+}
+
+// ------------------------------------------------------------------ match filtering: grid motion consensus
+
+static_assert(sizeof(gpc_support) == sizeof(gpc::ConsRec<false>) && sizeof(gpc_correspondence) == sizeof(gpc::ConsRec<true>),
+              "the records and the kernels' view of them");
+
+static int cons_params(const gpc_consensus* p) {
+  if (!p) return GPC_E_INVALID;
+  if (p->cell < 4 || p->cell > 256 || (p->cell & 1) || (p->shifts != 1 && p->shifts != 4)) return GPC_E_INVALID;
+  if (p->alpha_num < 0 || p->alpha_num > 1024 || p->alpha_den < 1 || p->alpha_den > 64) return GPC_E_INVALID;
+  return GPC_OK;
+}
+
+// S and T stay below 2^24 (the products of the test are exact, the kernels multiply 24-bit values), a cell index and a
+// class below 2^26, a record's number in the whole call below 2^31, and a launch has one grid row per pair
+static int cons_limits(long cap, int W, int H, int npairs, int cell) {
+  const long cw = ((long)W + cell - 1) / cell, ch = ((long)H + cell - 1) / cell;
+  if (cap > (1l << 23) || cw * ch > (1l << 22) || npairs > 65535 || (long)npairs * cap > 0x7FFFFFFFl) return GPC_E_UNSUPPORTED;
+  return GPC_OK;
+}
+
+static int cons_args(const gpc_hip_ctx* c, const void* rec, size_t esz, int cap, const void* counts, int W, int H, int npairs,
+                     const gpc_consensus* prm, const void* out, int cap_out, const void* out_counts) {
+  if (!c || !rec || !counts || !out || !out_counts || npairs < 1 || cap <= 0 || cap_out <= 0 || W <= 0 || H <= 0) return GPC_E_INVALID;
+  CHK(cons_params(prm));
+  CHK(cons_limits(cap, W, H, npairs, prm->cell));
+  const uintptr_t r0 = (uintptr_t)rec, r1 = r0 + esz * (size_t)npairs * (size_t)cap;
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + esz * (size_t)npairs * (size_t)cap_out;
+  if (r0 < o1 && o0 < r1) return GPC_E_INVALID;  // (kept records are written while later ones are still read)
+  return GPC_OK;
+}
+
+static gpc::ConsGrid cons_grid(int W, int H, const gpc_consensus* prm, int s) {
+  gpc::ConsGrid g;
+  const int cl = prm->cell;
+  g.W = W, g.H = H;
+  g.ox = (s & 1) ? cl / 2 : 0;
+  g.oy = (s & 2) ? cl / 2 : 0;
+  g.gx = (W - 1 + g.ox) / cl + 1;
+  g.gy = (H - 1 + g.oy) / cl + 1;
+  g.ncell = g.gx * g.gy;
+  g.kw = 2u * (uint32_t)g.gx - 1u;
+  g.dc = make_divw(cl);
+  g.dgx = make_divw(g.gx > 1 ? g.gx : 2);
+  g.bit = 1u << s;
+  g.kq = (uint32_t)(prm->alpha_den * prm->alpha_den);
+  g.an2 = (uint32_t)(prm->alpha_num * prm->alpha_num);
+  return g;
+}
+
+// The launches over records already on the device: four per grid, then three that compact.
+extern "C++" {
+template <bool CORR>
+static int cons_filter(gpc_hip_ctx* c, const void* d_rec, int cap, const int32_t* d_counts, int W, int H, int P,
+                       const gpc_consensus* prm, uint8_t* d_keep, void* d_out, int cap_out, int32_t* d_index,
+                       int32_t* d_out_counts) {
+  typedef gpc::ConsRec<CORR> Rec;
+  size_t maxcell = 0;
+  for (int s = 0; s < prm->shifts; ++s) maxcell = std::max(maxcell, (size_t)cons_grid(W, H, prm, s).ncell);
+  const long nchunk = ((long)cap + CS_CHUNK - 1) / CS_CHUNK;
+  CHK(ensure(c, c->cs_key, sizeof(uint32_t) * (size_t)cap * P));
+  CHK(ensure(c, c->cs_idx, sizeof(int32_t) * (size_t)cap * P));
+  CHK(ensure(c, c->cs_cur, sizeof(int32_t) * maxcell * P));
+  CHK(ensure(c, c->cs_start, sizeof(int32_t) * (maxcell + 1) * P));
+  CHK(ensure(c, c->cs_blk, sizeof(int32_t) * (size_t)nchunk * P));
+  if (!d_keep) {
+    CHK(ensure(c, c->cs_keep, (size_t)cap * P));
+    d_keep = (uint8_t*)c->cs_keep.p;
+  }
+  const Rec* rec = (const Rec*)d_rec;
+  uint32_t* skey = (uint32_t*)c->cs_key.p;
+  int32_t* sidx = (int32_t*)c->cs_idx.p;
+  int32_t* cur = (int32_t*)c->cs_cur.p;
+  int32_t* start = (int32_t*)c->cs_start.p;
+  int32_t* blk = (int32_t*)c->cs_blk.p;
+  const long nb = ((long)cap + CS_THREADS - 1) / CS_THREADS;
+  const dim3 sgrid((unsigned)(nb < 1024 ? nb : 1024), P), cgrid((unsigned)nchunk, P);
+  for (int s = 0; s < prm->shifts; ++s) {
+    const gpc::ConsGrid g = cons_grid(W, H, prm, s);
+    HIPCHK(c, hipMemsetAsync(cur, 0, sizeof(int32_t) * (size_t)g.ncell * P, c->stream));
+    {
+      Timed t(c, KID_CONS_CELLS);
+      hipLaunchKernelGGL((gpc::k_cons_cells<CORR>), sgrid, dim3(CS_THREADS), 0, c->stream, rec, cap, d_counts, g, cur, d_keep);
+    }
+    {
+      Timed t(c, KID_CONS_SCAN);
+      hipLaunchKernelGGL((gpc::k_cons_scan<true, true>), dim3(P), dim3(1024), 0, c->stream, cur, (long)g.ncell, g.ncell, start,
+                         (long)g.ncell + 1, (int32_t*)nullptr);
+    }
+    {
+      Timed t(c, KID_CONS_SCATTER);
+      hipLaunchKernelGGL((gpc::k_cons_scatter<CORR>), sgrid, dim3(CS_THREADS), 0, c->stream, rec, cap, d_counts, g, cur, skey, sidx);
+    }
+    {
+      Timed t(c, KID_CONS_COUNT);
+      hipLaunchKernelGGL(gpc::k_cons_count, dim3((unsigned)g.ncell, P), dim3(CS_THREADS), 0, c->stream, cap, g,
+                         (const int32_t*)start, (const uint32_t*)skey, (const int32_t*)sidx, d_keep);
+    }
+  }
+  {
+    Timed t(c, KID_CONS_BLOCKS);
+    hipLaunchKernelGGL(gpc::k_cons_blocks, cgrid, dim3(CS_THREADS), 0, c->stream, cap, d_counts, (const uint8_t*)d_keep, blk, (int)nchunk);
+  }
+  {
+    Timed t(c, KID_CONS_SCAN);
+    hipLaunchKernelGGL((gpc::k_cons_scan<false, false>), dim3(P), dim3(1024), 0, c->stream, blk, nchunk, (int)nchunk, blk, nchunk,
+                       d_out_counts);
+  }
+  {
+    Timed t(c, KID_CONS_WRITE);
+    hipLaunchKernelGGL((gpc::k_cons_write<CORR>), cgrid, dim3(CS_THREADS), 0, c->stream, rec, cap, d_counts, (const uint8_t*)d_keep,
+                       (const int32_t*)blk, (int)nchunk, (Rec*)d_out, cap_out, d_index);
+  }
+  for (int k = KID_CONS_CELLS; k <= KID_CONS_WRITE; ++k) {
+    const bool typed = k == KID_CONS_CELLS || k == KID_CONS_SCATTER || k == KID_CONS_WRITE;
+    // (the scan's slot times both of its instantiations: <true, true> once per grid, <false, false> once for the compaction)
+    snprintf(c->launch_name[k], sizeof c->launch_name[0], k == KID_CONS_SCAN ? "gpc::%s<true, true> + <false, false>" : (typed ? "gpc::%s<%s>" : "gpc::%s"),
+             kKernelNames[k], CORR ? "true" : "false");
+  }
+  HIPCHK(c, hipGetLastError());
+  return GPC_OK;
+}
+}  // extern "C++"
+
+int gpc_hip_consensus_supports_device(gpc_hip_ctx* c, const gpc_support* d_rec, int cap_per_pair, const int32_t* d_counts, int W,
+                                      int H, int npairs, const gpc_consensus* prm, uint8_t* d_keep, gpc_support* d_out, int cap_out,
+                                      int32_t* d_index, int32_t* d_out_counts) {
+  CHK(cons_args(c, d_rec, sizeof(gpc_support), cap_per_pair, d_counts, W, H, npairs, prm, d_out, cap_out, d_out_counts));
+  HIPCHK(c, hipSetDevice(c->device));
+  return cons_filter<false>(c, d_rec, cap_per_pair, d_counts, W, H, npairs, prm, d_keep, d_out, cap_out, d_index, d_out_counts);
+}
+
+int gpc_hip_consensus_correspondences_device(gpc_hip_ctx* c, const gpc_correspondence* d_rec, int cap_per_pair,
+                                             const int32_t* d_counts, int W, int H, int npairs, const gpc_consensus* prm,
+                                             uint8_t* d_keep, gpc_correspondence* d_out, int cap_out, int32_t* d_index,
+                                             int32_t* d_out_counts) {
+  CHK(cons_args(c, d_rec, sizeof(gpc_correspondence), cap_per_pair, d_counts, W, H, npairs, prm, d_out, cap_out, d_out_counts));
+  HIPCHK(c, hipSetDevice(c->device));
+  return cons_filter<true>(c, d_rec, cap_per_pair, d_counts, W, H, npairs, prm, d_keep, d_out, cap_out, d_index, d_out_counts);
+}
+
+int gpc_hip_consensus_batch_device(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H, int npairs,
+                                   const gpc_settings* s, const gpc_consensus* prm, gpc_support* d_out, int cap_out,
+                                   int32_t* d_out_counts, int32_t* d_raw_counts, int32_t* d_ncand) {
+  if (!c || !d_rawL || !d_rawR || !d_out || !d_out_counts || npairs <= 0 || cap_out <= 0) return GPC_E_INVALID;
+  CHK(cons_params(prm));
+  CHK(check_settings(s));
+  CHK(check_dims(W, H));
+  CHK(forest_matches(c, W, H));
+  const int G = c->ngroups > 1 ? c->ngroups : 1;
+  if (G > 1 && s->use_hashtable) return GPC_E_UNSUPPORTED;  // (as gpc_hip_match_batch_device, before any workspace is made)
+  // every record of every pair, as gpc_hip_score_batch_device keeps them
+  const long cap = (long)G * (W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;
+  CHK(cons_limits(cap, W, H, npairs, prm->cell));
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->pipeline > 1) CHK(drain_lanes(c));
+  CHK(ensure(c, c->sc_rec, sizeof(gpc_support) * (size_t)cap * npairs));
+  CHK(ensure(c, c->sc_cnt, sizeof(int32_t) * (size_t)npairs));
+  {
+    StrictScope strict(c);
+    CHK(gpc_hip_match_batch_device(c, d_rawL, d_rawR, W, H, npairs, s, (gpc_support*)c->sc_rec.p, (int)cap, (int32_t*)c->sc_cnt.p,
+                                   d_ncand));
+  }
+  if (d_raw_counts)
+    HIPCHK(c, hipMemcpyAsync(d_raw_counts, c->sc_cnt.p, sizeof(int32_t) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
+  return cons_filter<false>(c, c->sc_rec.p, (int)cap, (const int32_t*)c->sc_cnt.p, W, H, npairs, prm, nullptr, d_out, cap_out, nullptr,
+                            d_out_counts);
+}
+
+int gpc_hip_consensus_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W, int H, int nframes, const gpc_settings* s,
+                                      const gpc_consensus* prm, gpc_correspondence* d_out, int cap_out, int32_t* d_out_counts,
+                                      int32_t* d_raw_counts, int32_t* d_ncand) {
+  if (!c || !d_frames || !d_out || !d_out_counts || nframes < 2 || cap_out <= 0) return GPC_E_INVALID;
+  CHK(cons_params(prm));
+  CHK(check_settings(s));
+  CHK(check_dims(W, H));
+  CHK(forest_matches(c, W, H));
+  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
+  const int npairs = nframes - 1;
+  const long cap = (long)(W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;
+  CHK(cons_limits(cap, W, H, npairs, prm->cell));
+  HIPCHK(c, hipSetDevice(c->device));
+  CHK(ensure(c, c->sc_rec, sizeof(gpc_correspondence) * (size_t)cap * npairs));
+  CHK(ensure(c, c->sc_cnt, sizeof(int32_t) * (size_t)npairs));
+  CHK(gpc_hip_match_sequence_device(c, d_frames, W, H, nframes, s, (gpc_correspondence*)c->sc_rec.p, (int)cap, (int32_t*)c->sc_cnt.p,
+                                    d_ncand));
+  if (d_raw_counts)
+    HIPCHK(c, hipMemcpyAsync(d_raw_counts, c->sc_cnt.p, sizeof(int32_t) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
+  return cons_filter<true>(c, c->sc_rec.p, (int)cap, (const int32_t*)c->sc_cnt.p, W, H, npairs, prm, nullptr, d_out, cap_out, nullptr,
+                           d_out_counts);
+}
+
+// Host forms: chunks of at most 16 pairs staged in one device block (c->cs_stage).  Of a pair only its first m_t records
+// travel up, and only what the device form writes travels down, so the caller's arrays keep every other byte.
+extern "C++" {
+template <bool CORR>
+static int cons_host(gpc_hip_ctx* c, const void* rec, int cap, const int32_t* counts, int W, int H, int npairs,
+                     const gpc_consensus* prm, uint8_t* keep, void* out, int cap_out, int32_t* index, int32_t* out_counts) {
+  const size_t esz = sizeof(gpc::ConsRec<CORR>);
+  CHK(cons_args(c, rec, esz, cap, counts, W, H, npairs, prm, out, cap_out, out_counts));
+  CHK(score_host_begin(c));
+  const int K = npairs < 16 ? npairs : 16;
+  size_t off[7];
+  off[0] = 0;                                                    // records
+  off[1] = off[0] + pad16(esz * (size_t)cap * K);                // counts
+  off[2] = off[1] + pad16(sizeof(int32_t) * (size_t)K);          // keep
+  off[3] = off[2] + pad16((size_t)cap * K);                      // out
+  off[4] = off[3] + pad16(esz * (size_t)cap_out * K);            // index
+  off[5] = off[4] + pad16(sizeof(int32_t) * (size_t)cap_out * K);  // out_counts
+  off[6] = off[5] + pad16(sizeof(int32_t) * (size_t)K);
+  CHK(ensure(c, c->cs_stage, off[6]));
+  uint8_t* d = (uint8_t*)c->cs_stage.p;
+  int status = GPC_OK;
+  for (int p0 = 0; p0 < npairs; p0 += K) {
+    const int pc = npairs - p0 < K ? npairs - p0 : K;
+    CHK(track_upload(c, d + off[1], counts + p0, sizeof(int32_t) * (size_t)pc));
+    for (int t = 0; t < pc; ++t) {
+      const int m = counts[p0 + t] < 0 ? 0 : (counts[p0 + t] > cap ? cap : counts[p0 + t]);
+      CHK(track_upload(c, d + off[0] + esz * (size_t)t * cap, (const uint8_t*)rec + esz * (size_t)(p0 + t) * cap, esz * (size_t)m));
+    }
+    CHK(cons_filter<CORR>(c, d + off[0], cap, (const int32_t*)(d + off[1]), W, H, pc, prm, keep ? d + off[2] : nullptr, d + off[3],
+                          cap_out, index ? (int32_t*)(d + off[4]) : nullptr, (int32_t*)(d + off[5])));
+    CHK(pinned_counts(c, pc));
+    HIPCHK(c, hipMemcpyAsync(c->h_cnt, d + off[5], sizeof(int32_t) * (size_t)pc, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int t = 0; t < pc; ++t) {
+      const int m = counts[p0 + t] < 0 ? 0 : (counts[p0 + t] > cap ? cap : counts[p0 + t]);
+      const int n = c->h_cnt[t], w = n < cap_out ? n : cap_out;
+      if (n > cap_out) status = GPC_E_CAPACITY;
+      if (keep && m)
+        HIPCHK(c, hipMemcpyAsync(keep + (size_t)(p0 + t) * cap, d + off[2] + (size_t)t * cap, (size_t)m, hipMemcpyDeviceToHost, c->stream));
+      if (w > 0) {
+        HIPCHK(c, hipMemcpyAsync((uint8_t*)out + esz * (size_t)(p0 + t) * cap_out, d + off[3] + esz * (size_t)t * cap_out, esz * (size_t)w,
+                                 hipMemcpyDeviceToHost, c->stream));
+        if (index)
+          HIPCHK(c, hipMemcpyAsync(index + (size_t)(p0 + t) * cap_out, d + off[4] + sizeof(int32_t) * (size_t)t * cap_out,
+                                   sizeof(int32_t) * (size_t)w, hipMemcpyDeviceToHost, c->stream));
+      }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(out_counts + p0, c->h_cnt, sizeof(int32_t) * (size_t)pc);
+  }
+  CHK(check_join_err(c));
+  return status;
+}
+}  // extern "C++"
+
+int gpc_hip_consensus_supports(gpc_hip_ctx* c, const gpc_support* rec, int cap_per_pair, const int32_t* counts, int W, int H,
+                               int npairs, const gpc_consensus* prm, uint8_t* keep, gpc_support* out, int cap_out, int32_t* index,
+                               int32_t* out_counts) {
+  return cons_host<false>(c, rec, cap_per_pair, counts, W, H, npairs, prm, keep, out, cap_out, index, out_counts);
+}
+
+int gpc_hip_consensus_correspondences(gpc_hip_ctx* c, const gpc_correspondence* rec, int cap_per_pair, const int32_t* counts, int W,
+                                      int H, int npairs, const gpc_consensus* prm, uint8_t* keep, gpc_correspondence* out,
+                                      int cap_out, int32_t* index, int32_t* out_counts) {
+  return cons_host<true>(c, rec, cap_per_pair, counts, W, H, npairs, prm, keep, out, cap_out, index, out_counts);
 }
 
 int gpc_hip_match_batch_device_packed(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H,
