@@ -1,7 +1,11 @@
 // gpc_device.h -- shared device-side definitions for the gfx950 kernels.
 #pragma once
 
+// (A host-only compile -- no __HIPCC__ -- sees the constants and the host-made divisors and shard splits alone:
+// tests/cpp/divw_check.cpp includes this header as it stands.)
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 #define GPC_R 13                    // patch radius == candidate margin (inference.hpp:322)
@@ -50,7 +54,9 @@ struct GpcForestDev {
   int32_t tau_m128;   // one of these bytes is 0x80 (tau = -128): k_hash takes the complemented subtract that holds for every tau
 };
 
+#ifdef __HIPCC__
 __device__ __forceinline__ unsigned lane_id() { return threadIdx.x & 63u; }
+#endif
 
 // Pixel index k = y*W + x  ->  (x, y) without an integer division: for k < 2^31,
 // k / W == umulhi(k, ceil(2^(31+p) / W)) >> (p - 1) with p = ceil(log2 W)  (Granlund & Montgomery).
@@ -72,6 +78,48 @@ inline GpcDivW make_divw(int W) {
   return d;
 }
 
+// Ticket counters (shards of pairs) a fused join deals npairs pairs over when nothing is forced: what gpc_hip.hip's
+// join_shards explains and measures.  1 .. min(npairs, 13), never a multiple of 8 above 3 pairs.
+inline int join_shards_auto(int npairs) {
+  if (npairs <= 3) return npairs;
+  int best = 3;
+  long best_waste = -1;
+  for (int n = 3; n <= 13 && n <= npairs; ++n) {
+    if (n % 8 == 0) continue;
+    long waste = ((long)((npairs + n - 1) / n) * n - npairs) * 1000 / npairs;   // per mille of the launch the fullest shard runs alone
+    if (waste <= 15) waste = 0;                                                   // (below the boxes' run-to-run spread)
+    const int dn = n > 7 ? n - 7 : 7 - n, db = best > 7 ? best - 7 : 7 - best;
+    const bool nearer = dn < db;
+    if (best_waste < 0 || waste < best_waste || (waste == best_waste && nearer)) {
+      best = n;
+      best_waste = waste;
+    }
+  }
+  return best;
+}
+
+// npairs pairs over nshards ticket counters (k_rowjoin_fused.h, RjfArgs): shards below n_hi hold ps[0] pairs, the others
+// ps[1]; ticket g of a shard is row g / ps of its pair g % ps, the quotient by make_divw's multiply-high (a shard of one
+// pair divides by nothing: the kernel skips the multiply, the magic is that of 2).
+struct GpcJoinSplit {
+  int n_hi;
+  int ps[2];
+  uint32_t ps_magic[2];
+  int ps_sh[2];
+};
+inline GpcJoinSplit make_join_split(int npairs, int nshards) {
+  GpcJoinSplit s;
+  s.n_hi = npairs % nshards;
+  s.ps[0] = npairs / nshards + (s.n_hi ? 1 : 0);
+  s.ps[1] = npairs / nshards;
+  for (int k = 0; k < 2; ++k) {
+    const GpcDivW dv = make_divw(s.ps[k] > 1 ? s.ps[k] : 2);
+    s.ps_magic[k] = dv.magic;
+    s.ps_sh[k] = dv.sh;
+  }
+  return s;
+}
+
 // ndb::Hashmatch's bucket of a 64-bit state (y << 32 | code) % 214673 (hashmatch.hpp:252-263) without 64-bit division:
 // 2^32 mod 214673 = 4585, and x mod 214673 for a 32-bit x by a multiply-high whose quotient is at most one short
 // (checked on the host for every 32-bit x and for 5e7 random states).
@@ -90,6 +138,7 @@ __device__ __forceinline__ uint32_t hm_bucket(uint32_t code, uint32_t y) {  // y
 }
 #endif
 
+#ifdef __HIPCC__
 __device__ __forceinline__ unsigned long long lanemask_lt() {
   return (1ull << lane_id()) - 1ull;
 }
@@ -149,3 +198,4 @@ __device__ __forceinline__ void block_exscan(uint32_t* __restrict__ arr, uint32_
   if (TOTAL && tid == NT - 1) arr[NT * SPT] = base;
   __syncthreads();
 }
+#endif  // __HIPCC__

@@ -955,20 +955,7 @@ int check_join_err(gpc_hip_ctx* c) {
 // So: 3 .. 13 shards, not a multiple of 8, the least time the fullest shard runs alone; ties go to the count nearest 7.
 int join_shards(const gpc_hip_ctx* c, int npairs) {
   if (c->fuse_shards > 0) return npairs < c->fuse_shards ? npairs : c->fuse_shards;
-  if (npairs <= 3) return npairs;
-  int best = 3;
-  long best_waste = -1;
-  for (int n = 3; n <= 13 && n <= npairs; ++n) {
-    if (n % 8 == 0) continue;
-    long waste = ((long)((npairs + n - 1) / n) * n - npairs) * 1000 / npairs;   // per mille of the launch the fullest shard runs alone
-    if (waste <= 15) waste = 0;                                                   // (below the boxes' run-to-run spread)
-    const bool nearer = abs(n - 7) < abs(best - 7);
-    if (best_waste < 0 || waste < best_waste || (waste == best_waste && nearer)) {
-      best = n;
-      best_waste = waste;
-    }
-  }
-  return best;
+  return join_shards_auto(npairs);  // (gpc_device.h: reachable by a host-only compile)
 }
 
 // State of the fused join: ticket counters + one granule per (pair, row); zeroed when (re)allocated, then kept
@@ -1088,13 +1075,12 @@ int run_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, i
     if (nsh > nwg) nsh = (int)nwg;                                                                              \
     a.nshards = nsh;                                                                                            \
     if (c->debug) fprintf(stderr, "[gpc_hip] k_row_join_fused<%d, %d>: %d workgroups per CU by the occupancy API, %ld workgroups, %d shards, %zu B of LDS\n", SPT, NT, per_cu, nwg, nsh, lds); \
-    a.n_hi = npairs % nsh;                                                                                      \
-    a.ps[0] = npairs / nsh + (a.n_hi ? 1 : 0);                                                                  \
-    a.ps[1] = npairs / nsh;                                                                                     \
+    const GpcJoinSplit sp_ = make_join_split(npairs, nsh);                                                      \
+    a.n_hi = sp_.n_hi;                                                                                          \
     for (int k_ = 0; k_ < 2; ++k_) {                                                                            \
-      const GpcDivW dv_ = make_divw(a.ps[k_] > 1 ? a.ps[k_] : 2);                                     \
-      a.ps_magic[k_] = dv_.magic;                                                                               \
-      a.ps_sh[k_] = dv_.sh;                                                                                     \
+      a.ps[k_] = sp_.ps[k_];                                                                                    \
+      a.ps_magic[k_] = sp_.ps_magic[k_];                                                                        \
+      a.ps_sh[k_] = sp_.ps_sh[k_];                                                                              \
     }                                                                                                           \
     hipLaunchKernelGGL((gpc::k_row_join_fused<SPT, NT, WIDE>), dim3((unsigned)nwg), dim3(NT), lds, c->stream, a); \
   } while (0)
