@@ -200,7 +200,7 @@ struct gpc_hip_ctx {
   void* h_in = nullptr;           // page-locked bounce buffer for PAGEABLE input images (2 slots x 2 sides x a chunk)
   size_t h_in_cap = 0;
   int32_t* h_cnt = nullptr;       // page-locked landing area of counts [npairs] + candidate counts [npairs][2]: a copy to the
-  size_t h_cnt_cap = 0;           // caller's (pageable) arrays would block the host until the chunk's kernels are done
+  size_t h_cnt_cap = 0;           // caller's (pageable) arrays would block the host until the chunk's kernels are done (bytes)
   ExpandPool pool;
   // host clock at the stages of the last gpc_hip_match_batch / _packed call, ms since its entry (gpc_hip_batch_stages):
   // [0] last upload seen complete, [1] last chunk's kernels done (its counts have arrived), [2] last chunk of packed
@@ -253,15 +253,17 @@ struct gpc_hip_ctx {
   bool gtau = false;           // one of the groups has a nonzero tau
   DevBuf gforest_dev;          // [3][GPC_MAX_GROUPS] GpcForestDev: SSE order, Naive order, SSE with the tall tile's offsets
   DevBuf vstats, vcand, vout, vcnt, vncand, uplane, ublk, gdense;  // virtual-pair statistics / candidates / results, union state
-  // scoring (gpc_hip_score_*): every record of every pair of a match-and-score call and their counts; the host forms' chunk
-  // of images and truth, and its scores
-  DevBuf sc_rec, sc_cnt, sc_in, sc_out;
-  // point tracks (gpc_hip_track_*): per-pixel planes of pairs 1 .. P-1, predecessor per record, head counts per chunk; the host
-  // forms' staging block (frames or records in, records, links, ids and table out)
-  DevBuf tr_plane, tr_pred, tr_blk, tr_stage;
+  // match-and-score, match-and-filter (all_records): every record of every pair of the call and their counts
+  DevBuf all_rec, all_cnt;
+  // the host forms of scoring, tracks and filtering (Stage): what a call or a chunk of it sends up and brings down; the
+  // copies that read a piece of the transfer arena are done
+  DevBuf stage;
+  hipEvent_t e_stage[2] = {};
+  // point tracks (gpc_hip_track_*): per-pixel planes of pairs 1 .. P-1, predecessor per record, head counts per chunk
+  DevBuf tr_plane, tr_pred, tr_blk;
   // match filtering (gpc_hip_consensus_*): class and record index per sorted position, cursors and first positions per pair
-  // and grid cell, kept records per chunk, the keep mask where the caller wants none; the host forms' staging block
-  DevBuf cs_key, cs_idx, cs_cur, cs_start, cs_blk, cs_keep, cs_stage;
+  // and grid cell, kept records per chunk, the keep mask where the caller wants none
+  DevBuf cs_key, cs_idx, cs_cur, cs_start, cs_blk, cs_keep;
   DevBuf sstats;  // frame sequences: the frames' statistics expanded into the pair layout [npairs*2] (k_seq_stats)
 
   // workspaces
@@ -1654,6 +1656,19 @@ int forest_matches(gpc_hip_ctx* c, int W, int H) {
   return GPC_OK;
 }
 
+// settings, dimensions and forest are usable for a match of pairs (seq: of consecutive frames).  Group mode has no
+// hash-table matcher and no sequences.
+int match_usable(gpc_hip_ctx* c, const gpc_settings* s, int W, int H, bool seq) {
+  CHK(check_settings(s));
+  CHK(check_dims(W, H));
+  CHK(forest_matches(c, W, H));
+  if (c->ngroups > 1 && (seq || s->use_hashtable)) return GPC_E_UNSUPPORTED;
+  return GPC_OK;
+}
+
+// the records of a pair that are there to be read or copied: its count may be negative, or larger than its capacity
+inline int valid_records(int count, int cap) { return count < 0 ? 0 : (count > cap ? cap : count); }
+
 // The device's address of page-locked host memory the GPU can write (hipHostMalloc / gpc_hip_host_alloc), or null.
 void* device_view_of_host(const void* p) {
   hipPointerAttribute_t a;
@@ -1782,6 +1797,19 @@ int xfer_reserve(gpc_hip_ctx* c, size_t bytes, uint8_t** dev) {
   return GPC_OK;
 }
 
+// at least `bytes` of the page-locked landing area of small per-pair words
+int pinned_area(gpc_hip_ctx* c, size_t bytes) {
+  if (bytes <= c->h_cnt_cap) return GPC_OK;
+  if (c->h_cnt) HIPCHK(c, hipHostFree(c->h_cnt));
+  c->h_cnt = nullptr;
+  c->h_cnt_cap = 0;
+  HIPCHK(c, hipHostMalloc((void**)&c->h_cnt, bytes, hipHostMallocDefault));
+  c->h_cnt_cap = bytes;
+  return GPC_OK;
+}
+// ... for npairs counts + 2 * npairs candidate counts
+int pinned_counts(gpc_hip_ctx* c, int npairs) { return pinned_area(c, sizeof(int32_t) * 3 * (size_t)npairs); }
+
 // dst[0 .. bytes) = src[0 .. bytes) by a kernel (device memory or device views of page-locked host memory; both 16-byte
 // aligned, bytes a multiple of 16): no copy-engine submission, no runtime staging
 int dev_copy16(gpc_hip_ctx* c, void* dst, const void* src, size_t bytes) {
@@ -1863,6 +1891,19 @@ int ensure_lanes(gpc_hip_ctx* c) {
 int drain_lanes(gpc_hip_ctx* c) {
   for (auto& l : c->lanes)
     if (l.s && l.used) HIPCHK(c, hipStreamSynchronize(l.s));
+  return GPC_OK;
+}
+
+// A host entry point that fills the transfer arena begins: what a _begin queued may still be writing its results there, so
+// it is waited for, and ended as every later call on the context ends it; then the lanes are drained.
+int host_call_begin(gpc_hip_ctx* c) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->pend.active || c->pre_slot >= 0) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->pend.active = false;
+    c->pre_slot = -1;
+  }
+  if (c->pipeline > 1) CHK(drain_lanes(c));
   return GPC_OK;
 }
 
@@ -2121,8 +2162,8 @@ int gpc_hip_destroy(gpc_hip_ctx* c) {
                     &c->gvals[0], &c->gvals[1], &c->ghist, &c->gmisc, &c->hkeys[0], &c->hkeys[1],
                     &c->hvals[0], &c->hvals[1], &c->hrec, &c->forest_dev, &c->packed, &c->gpart, &c->jstate, &c->gkv,
                     &c->res_smooth, &c->res_grad, &c->ext_raw, &c->ext_smooth, &c->ext_grad, &c->ext_groups,
-                    &c->sstats, &c->sc_rec, &c->sc_cnt, &c->sc_in, &c->sc_out, &c->tr_plane, &c->tr_pred, &c->tr_blk,
-                    &c->tr_stage, &c->cs_key, &c->cs_idx, &c->cs_cur, &c->cs_start, &c->cs_blk, &c->cs_keep, &c->cs_stage};
+                    &c->sstats, &c->all_rec, &c->all_cnt, &c->stage, &c->tr_plane, &c->tr_pred, &c->tr_blk,
+                    &c->cs_key, &c->cs_idx, &c->cs_cur, &c->cs_start, &c->cs_blk, &c->cs_keep};
   while (!c->train_sets.empty()) (void)gpc_hip_train_set_destroy(c, c->train_sets.back());
   for (DevBuf* b : bufs) release(*b);
   for (auto& s : c->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -2140,6 +2181,8 @@ int gpc_hip_destroy(gpc_hip_ctx* c) {
   }
   if (c->e_flag) (void)hipEventDestroy(c->e_flag);
   if (c->e_pre) (void)hipEventDestroy(c->e_pre);
+  for (hipEvent_t e : c->e_stage)
+    if (e) (void)hipEventDestroy(e);
   for (auto& l : c->lanes) {
     if (l.s) {
       (void)hipStreamSynchronize(l.s);
@@ -2677,8 +2720,6 @@ int gpc_hip_hash_codes_groups(gpc_hip_ctx* c, const uint8_t* smooth, const uint8
   return GPC_OK;
 }
 
-static int pinned_counts(gpc_hip_ctx* c, int npairs);
-
 // Queues hash + match of two preprocessed images; the results go to the transfer arena (cap_dev records at most; the
 // caller's page-locked array instead when direct_out is its device view) and are collected by match_fetch.
 static int match_preprocessed_begin(gpc_hip_ctx* c, const uint8_t* smoothL, const uint8_t* gradL,
@@ -2986,17 +3027,6 @@ int gpc_hip_debug_pipeline_events(gpc_hip_ctx* c, void* wait_before_preprocess, 
   return GPC_OK;
 }
 
-// page-locked landing area for npairs counts + 2*npairs candidate counts
-static int pinned_counts(gpc_hip_ctx* c, int npairs) {
-  if ((size_t)npairs * 3 <= c->h_cnt_cap) return GPC_OK;
-  if (c->h_cnt) HIPCHK(c, hipHostFree(c->h_cnt));
-  c->h_cnt = nullptr;
-  c->h_cnt_cap = 0;
-  HIPCHK(c, hipHostMalloc((void**)&c->h_cnt, sizeof(int32_t) * 3 * (size_t)npairs, hipHostMallocDefault));
-  c->h_cnt_cap = (size_t)npairs * 3;
-  return GPC_OK;
-}
-
 static int batch_streams(gpc_hip_ctx* c) {
   if (c->s_in) return GPC_OK;
   HIPCHK(c, hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking));
@@ -3157,10 +3187,7 @@ static int match_batch_unpacked(gpc_hip_ctx* c, const uint8_t* rawL, const uint8
 int gpc_hip_match_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W, int H, int nframes, const gpc_settings* s,
                                   gpc_correspondence* d_out, int cap_per_pair, int32_t* d_counts, int32_t* d_ncand) {
   if (!c || !d_frames || !d_out || !d_counts || nframes < 2 || cap_per_pair <= 0) return GPC_E_INVALID;
-  CHK(check_settings(s));
-  CHK(check_dims(W, H));
-  CHK(forest_matches(c, W, H));
-  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
+  CHK(match_usable(c, s, W, H, true));
   HIPCHK(c, hipSetDevice(c->device));
   if (c->pipeline > 1) CHK(drain_lanes(c));  // (sequences run on the context itself)
   const size_t n = (size_t)W * H;
@@ -3186,19 +3213,8 @@ int gpc_hip_match_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W
 int gpc_hip_match_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, int nframes, const gpc_settings* s,
                            gpc_correspondence* out, int cap, int32_t* counts, int32_t* ncand) {
   if (!c || !frames || !out || !counts || nframes < 2 || cap <= 0) return GPC_E_INVALID;
-  CHK(check_settings(s));
-  CHK(check_dims(W, H));
-  CHK(forest_matches(c, W, H));
-  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->pend.active || c->pre_slot >= 0) {
-    // what a _begin queued may still be writing its results into the page-locked arena this call fills with frames:
-    // it is waited for, and ended as every later call on the context ends it
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->pend.active = false;
-    c->pre_slot = -1;
-  }
-  if (c->pipeline > 1) CHK(drain_lanes(c));
+  CHK(match_usable(c, s, W, H, true));
+  CHK(host_call_begin(c));
   const size_t n = (size_t)W * H;
   const int npairs = nframes - 1;
   const int K = c->seq_frames > 0 ? c->seq_frames : 16;
@@ -3374,8 +3390,15 @@ int gpc_hip_score_correspondences_device(gpc_hip_ctx* c, const gpc_correspondenc
   return score_records_entry(c, d_corr, true, cap_per_pair, d_counts, W, H, npairs, truth, thr, n_thr, d_scores);
 }
 
-// lanes = 1 for the duration of a match-and-score call: it runs on the context itself
+// Every record of every pair of a call, kept on the device: what match-and-score and match-and-filter work on.  A group has
+// at most one record per left candidate, a union at most G.
 namespace {
+struct AllRecords {
+  void* rec;        // [npairs][cap]: gpc_support of pairs, gpc_correspondence of frames
+  int32_t* counts;  // [npairs]
+  int cap;
+};
+// lanes = 1 for the duration of the match: it runs on the context itself
 struct StrictScope {
   gpc_hip_ctx* c;
   int lanes;
@@ -3384,114 +3407,156 @@ struct StrictScope {
 };
 }  // namespace
 
-int gpc_hip_score_batch_device(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H, int npairs,
-                               const gpc_settings* s, const gpc_truth* truth, const float* thr, int n_thr, gpc_score* d_scores) {
-  if (!c || !d_rawL || !d_rawR || !d_scores || npairs <= 0) return GPC_E_INVALID;
-  CHK(truth_ok(truth, false));
+// what the match itself refuses is refused here, and a capacity that does not fit an int, before any workspace is made
+static int all_records_cap(gpc_hip_ctx* c, const gpc_settings* s, int W, int H, bool seq, int* cap) {
+  CHK(match_usable(c, s, W, H, seq));
+  const long n = (long)(c->ngroups > 1 ? c->ngroups : 1) * (W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;
+  if (n > 0x7FFFFFFFl) return GPC_E_UNSUPPORTED;
+  *cap = (int)n;
+  return GPC_OK;
+}
+
+// d_b null: d_a holds npairs + 1 frames; else d_a and d_b hold the left and right images of npairs pairs.  r->cap is what
+// all_records_cap gave for the call (filtering checks its own limits against it in between)
+static int all_records(gpc_hip_ctx* c, const uint8_t* d_a, const uint8_t* d_b, int W, int H, int npairs, const gpc_settings* s,
+                       int32_t* d_ncand, AllRecords* r) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->pipeline > 1) CHK(drain_lanes(c));
+  CHK(ensure(c, c->all_rec, (d_b ? sizeof(gpc_support) : sizeof(gpc_correspondence)) * (size_t)r->cap * npairs));
+  CHK(ensure(c, c->all_cnt, sizeof(int32_t) * (size_t)npairs));
+  r->rec = c->all_rec.p;
+  r->counts = (int32_t*)c->all_cnt.p;
+  if (!d_b) return gpc_hip_match_sequence_device(c, d_a, W, H, npairs + 1, s, (gpc_correspondence*)r->rec, r->cap, r->counts, d_ncand);
+  StrictScope strict(c);
+  return gpc_hip_match_batch_device(c, d_a, d_b, W, H, npairs, s, (gpc_support*)r->rec, r->cap, r->counts, d_ncand);
+}
+
+// match and score, images as all_records takes them: disparities of pairs, flow of frames
+static int score_match(gpc_hip_ctx* c, const uint8_t* d_a, const uint8_t* d_b, int W, int H, int npairs, const gpc_settings* s,
+                       const gpc_truth* truth, const float* thr, int n_thr, gpc_score* d_scores) {
+  const bool flow = !d_b;
+  CHK(truth_ok(truth, flow));
   CHK(truth_aligned(truth));
   gpc::ScoreThr t;
   CHK(score_thresholds(thr, n_thr, t));
-  CHK(check_settings(s));
-  CHK(check_dims(W, H));
-  CHK(forest_matches(c, W, H));
-  const int G = c->ngroups > 1 ? c->ngroups : 1;
-  if (G > 1 && s->use_hashtable) return GPC_E_UNSUPPORTED;  // (as gpc_hip_match_batch_device, before any workspace is made)
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->pipeline > 1) CHK(drain_lanes(c));
-  // every record of every pair: a group has at most one record per left candidate, a union at most G
-  const long cap = (long)G * (W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;
-  if (cap > 0x7FFFFFFFl) return GPC_E_UNSUPPORTED;
-  CHK(ensure(c, c->sc_rec, sizeof(gpc_support) * (size_t)cap * npairs));
-  CHK(ensure(c, c->sc_cnt, sizeof(int32_t) * (size_t)npairs));
-  {
-    StrictScope strict(c);
-    CHK(gpc_hip_match_batch_device(c, d_rawL, d_rawR, W, H, npairs, s, (gpc_support*)c->sc_rec.p, (int)cap,
-                                   (int32_t*)c->sc_cnt.p, nullptr));
-  }
-  CHK(score_records(c, c->sc_rec.p, false, cap, (const int32_t*)c->sc_cnt.p, W, H, npairs, truth, t, d_scores));
-  return score_matchable(c, false, 2, W, H, npairs, truth, d_scores);
+  AllRecords r;
+  CHK(all_records_cap(c, s, W, H, flow, &r.cap));
+  CHK(all_records(c, d_a, d_b, W, H, npairs, s, nullptr, &r));
+  CHK(score_records(c, r.rec, flow, r.cap, r.counts, W, H, npairs, truth, t, d_scores));
+  return score_matchable(c, flow, flow ? 1 : 2, W, H, npairs, truth, d_scores);
+}
+
+int gpc_hip_score_batch_device(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H, int npairs,
+                               const gpc_settings* s, const gpc_truth* truth, const float* thr, int n_thr, gpc_score* d_scores) {
+  if (!c || !d_rawL || !d_rawR || !d_scores || npairs <= 0) return GPC_E_INVALID;
+  return score_match(c, d_rawL, d_rawR, W, H, npairs, s, truth, thr, n_thr, d_scores);
 }
 
 int gpc_hip_score_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W, int H, int nframes, const gpc_settings* s,
                                   const gpc_truth* truth, const float* thr, int n_thr, gpc_score* d_scores) {
   if (!c || !d_frames || !d_scores || nframes < 2) return GPC_E_INVALID;
-  CHK(truth_ok(truth, true));
-  CHK(truth_aligned(truth));
-  gpc::ScoreThr t;
-  CHK(score_thresholds(thr, n_thr, t));
-  CHK(check_settings(s));
-  CHK(check_dims(W, H));
-  CHK(forest_matches(c, W, H));
-  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
-  HIPCHK(c, hipSetDevice(c->device));
-  const int npairs = nframes - 1;
-  const long cap = (long)(W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;
-  CHK(ensure(c, c->sc_rec, sizeof(gpc_correspondence) * (size_t)cap * npairs));
-  CHK(ensure(c, c->sc_cnt, sizeof(int32_t) * (size_t)npairs));
-  CHK(gpc_hip_match_sequence_device(c, d_frames, W, H, nframes, s, (gpc_correspondence*)c->sc_rec.p, (int)cap,
-                                    (int32_t*)c->sc_cnt.p, nullptr));
-  CHK(score_records(c, c->sc_rec.p, true, cap, (const int32_t*)c->sc_cnt.p, W, H, npairs, truth, t, d_scores));
-  return score_matchable(c, true, 1, W, H, npairs, truth, d_scores);
+  return score_match(c, d_frames, nullptr, W, H, nframes - 1, s, truth, thr, n_thr, d_scores);
 }
 
-// Host forms: chunks of at most 16 pairs (frames) through the device forms.  A chunk's images and truth planes are laid out
-// back to back in c->sc_in; pageable arrays pass through the page-locked arena (host_copy), page-locked ones are read where
-// they lie.  One wait per chunk: the arena and sc_in are reused by the next.
+// Host forms of scoring, tracks and filtering: lay out -> upload -> device form -> download, over ONE device block
+// (c->stage) that a call lays out anew: every host form waits for its stream before it returns, so no two are live together.
+//   layout:   in() and out() name the regions in order, each on a 16-byte boundary; alloc() then grows the block once.
+//   upload:   page-locked arrays (gpc_hip_host_alloc) are read where they lie.  Pageable ones pass through the page-locked
+//             arena (host_copy) in pieces of at most 32 MiB, two of them where one does not hold the regions a call (a
+//             chunk) uploads: a piece is written again only when the copies that read it are done (its event, or
+//             wait()).  Two, so that a scoring chunk above 32 MiB (16 pairs of 1024x436 with flow truth: 65 MB) still
+//             goes up without the host waiting for the device, as it did when scoring reserved a chunk's whole size;
+//             tracks and filtering, which had one piece and a wait behind every copy, now hold up to 64 MiB page-locked.
+//             in_bytes counts a records region in full, so two pieces may be reserved where the valid records fit one.
+//             Tracks and filtering send only the valid records of a pair (up_records).
+//   download: small per-pair words land in the page-locked h_cnt and are copied out after the wait; per-pair arrays go to
+//             the caller's arrays as they are, clipped to what the device form wrote, so every other byte there stays.
+// Scoring goes in chunks of at most 16 pairs (frames: GPC_HIP_SEQ_FRAMES, consecutive chunks share one), one wait per chunk;
+// tracks stage the whole call, since links cross pairs; filtering goes in chunks of at most 16 pairs.
 namespace {
-struct ScorePlane {
-  const uint8_t* src;  // host array of the whole call (null: absent)
-  size_t per_item;     // bytes per pair / frame
+struct Stage {
+  gpc_hip_ctx* c;
+  size_t bytes = 0, in_bytes = 0;  // the block; its regions that are uploaded
+  size_t piece = 0, at = 0;        // the arena of this call's pageable uploads: one or two pieces; the fill of the current one
+  int pieces = 0, cur = 0;
+  bool busy[2] = {false, false};   // copies queued since the last wait() may still read the piece: e_stage[k] says when they are done
+  explicit Stage(gpc_hip_ctx* ctx) : c(ctx) {}
+  size_t out(size_t n) {
+    const size_t region = bytes;
+    bytes += pad16(n);
+    return region;
+  }
+  size_t in(size_t n) {
+    in_bytes += pad16(n);
+    return out(n);
+  }
+  int alloc(size_t word_bytes) {  // word_bytes: what the call lands in h_cnt at a time
+    CHK(ensure(c, c->stage, bytes));
+    return pinned_area(c, word_bytes);
+  }
+  uint8_t* p(size_t region) const { return (uint8_t*)c->stage.p + region; }
+  int wait() {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    at = 0;
+    busy[0] = busy[1] = false;
+    return GPC_OK;
+  }
+  int next_piece() {  // the other piece (where there is one) is filled while the copies out of this one run
+    HIPCHK(c, hipEventRecord(c->e_stage[cur], c->stream));
+    busy[cur] = true;
+    cur = (cur + 1) % pieces;
+    at = 0;
+    if (busy[cur]) HIPCHK(c, hipEventSynchronize(c->e_stage[cur]));
+    busy[cur] = false;
+    return GPC_OK;
+  }
+  int copy_up(size_t region, const uint8_t* src, size_t n, bool pinned) {
+    if (pinned && n) HIPCHK(c, hipMemcpyAsync(p(region), src, n, hipMemcpyHostToDevice, c->stream));
+    if (pinned || !n) return GPC_OK;
+    if (!piece) {  // (once per call)
+      piece = std::min(std::max(in_bytes, pad16(n)), (size_t)32 << 20);
+      pieces = in_bytes > piece ? 2 : 1;
+      uint8_t* d_arena = nullptr;
+      CHK(xfer_reserve(c, pieces * piece, &d_arena));
+      CHK(ensure_pool(c));
+      for (int k = 0; k < pieces; ++k)
+        if (!c->e_stage[k]) HIPCHK(c, hipEventCreateWithFlags(&c->e_stage[k], hipEventDisableTiming));
+    }
+    for (size_t done = 0; done < n;) {
+      if (at == piece) CHK(next_piece());
+      const size_t nb = std::min(n - done, piece - at);
+      uint8_t* h = c->h_xfer + cur * piece + at;
+      host_copy(c, h, src + done, nb, true);
+      host_copy_wait(c);
+      HIPCHK(c, hipMemcpyAsync(p(region) + done, h, nb, hipMemcpyHostToDevice, c->stream));
+      at += pad16(nb);
+      done += nb;
+    }
+    return GPC_OK;
+  }
+  int up(size_t region, const void* src, size_t n) { return copy_up(region, (const uint8_t*)src, n, device_view_of_host(src) != nullptr); }
+  // pairs [p0, p0 + pc) of src [..][cap] records of esz bytes -> region [pc][cap]: what lies beyond a pair's count is never read
+  int up_records(size_t region, const void* src, size_t esz, int cap, const int32_t* counts, int p0, int pc) {
+    const bool pinned = device_view_of_host(src) != nullptr;
+    for (int t = 0; t < pc; ++t)
+      CHK(copy_up(region + esz * (size_t)t * cap, (const uint8_t*)src + esz * (size_t)(p0 + t) * cap,
+                  esz * (size_t)valid_records(counts[p0 + t], cap), pinned));
+    return GPC_OK;
+  }
+  // (a pageable dst is written as it is, not through the arena as the note at h_xfer has it: that would be decided here)
+  int down(void* dst, size_t region, size_t n) {
+    HIPCHK(c, hipMemcpyAsync(dst, p(region), n, hipMemcpyDeviceToHost, c->stream));
+    return GPC_OK;
+  }
 };
 }  // namespace
 
-// items [i0, i0 + cnt[k]) of plane k -> sc_in at dev_off[k]
-static int score_upload(gpc_hip_ctx* c, const ScorePlane* planes, const size_t* first, const size_t* cnt, const size_t* dev_off,
-                        int nplanes) {
-  size_t pageable = 0;
-  for (int k = 0; k < nplanes; ++k)
-    if (planes[k].src && !device_view_of_host(planes[k].src)) pageable += pad16(planes[k].per_item * cnt[k]);
-  uint8_t* d_arena = nullptr;
-  if (pageable) {
-    CHK(xfer_reserve(c, pageable, &d_arena));
-    CHK(ensure_pool(c));
-  }
-  size_t at = 0;
-  for (int k = 0; k < nplanes; ++k) {
-    if (!planes[k].src) continue;
-    const size_t bytes = planes[k].per_item * cnt[k];
-    const uint8_t* src = planes[k].src + planes[k].per_item * first[k];
-    if (!device_view_of_host(planes[k].src)) {
-      host_copy(c, c->h_xfer + at, src, bytes, true);
-      src = c->h_xfer + at;
-      at += pad16(bytes);
-    }
-    host_copy_wait(c);
-    HIPCHK(c, hipMemcpyAsync((uint8_t*)c->sc_in.p + dev_off[k], src, bytes, hipMemcpyHostToDevice, c->stream));
-  }
-  return GPC_OK;
-}
-
-// at least `bytes` of the page-locked counts area (pinned_counts sizes it in pairs: three int32 each)
-static int pinned_bytes(gpc_hip_ctx* c, size_t bytes) { return pinned_counts(c, (int)((bytes + 3 * sizeof(int32_t) - 1) / (3 * sizeof(int32_t)))); }
-
-// a chunk's scores -> the caller's array (through the page-locked counts area: 120 bytes per pair), then the chunk is done
-static int score_download(gpc_hip_ctx* c, gpc_score* scores, int n) {
-  CHK(pinned_bytes(c, sizeof(gpc_score) * (size_t)n));
-  HIPCHK(c, hipMemcpyAsync(c->h_cnt, c->sc_out.p, sizeof(gpc_score) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  memcpy(scores, c->h_cnt, sizeof(gpc_score) * (size_t)n);
-  return check_join_err(c);
-}
-
-static int score_host_begin(gpc_hip_ctx* c) {
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->pend.active || c->pre_slot >= 0) {  // (a pending _begin may still write the arena: waited for and ended)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->pend.active = false;
-    c->pre_slot = -1;
-  }
-  if (c->pipeline > 1) CHK(drain_lanes(c));
-  return GPC_OK;
+// a chunk's scores -> the caller's array (120 bytes per pair: through h_cnt), then the chunk is done
+static int score_down(Stage& st, size_t region, gpc_score* scores, int n) {
+  CHK(st.down(st.c->h_cnt, region, sizeof(gpc_score) * (size_t)n));
+  CHK(st.wait());
+  memcpy(scores, st.c->h_cnt, sizeof(gpc_score) * (size_t)n);
+  return check_join_err(st.c);
 }
 
 // records, counts and truth of at most 16 pairs at a time through the records form
@@ -3502,29 +3567,25 @@ static int score_records_host(gpc_hip_ctx* c, const void* rec, bool corr, int ca
   CHK(truth_ok(truth, corr));
   gpc::ScoreThr t;
   CHK(score_thresholds(thr, n_thr, t));
-  CHK(score_host_begin(c));
+  CHK(host_call_begin(c));
   const size_t n = (size_t)W * H, esz = corr ? sizeof(gpc_correspondence) : sizeof(gpc_support);
   const int K = npairs < 16 ? npairs : 16;
-  size_t off[5];
-  off[0] = 0;
-  off[1] = pad16(esz * (size_t)cap * K);
-  off[2] = off[1] + pad16(sizeof(int32_t) * (size_t)K);
-  off[3] = off[2] + pad16(sizeof(float) * n * K);
-  off[4] = off[3] + (corr ? pad16(sizeof(float) * n * K) : 0);
-  CHK(ensure(c, c->sc_in, off[4] + n * K));
-  CHK(ensure(c, c->sc_out, sizeof(gpc_score) * (size_t)K));
-  const ScorePlane planes[5] = {{(const uint8_t*)rec, esz * (size_t)cap}, {(const uint8_t*)counts, sizeof(int32_t)},
-                                {(const uint8_t*)truth->u, sizeof(float) * n}, {(const uint8_t*)truth->v, sizeof(float) * n},
-                                {truth->ignore, n}};
+  Stage st(c);
+  const size_t r_rec = st.in(esz * (size_t)cap * K), r_cnt = st.in(sizeof(int32_t) * (size_t)K), r_u = st.in(sizeof(float) * n * K);
+  const size_t r_v = st.in(corr ? sizeof(float) * n * K : 0), r_ign = st.in(truth->ignore ? n * K : 0);
+  const size_t r_sc = st.out(sizeof(gpc_score) * (size_t)K);
+  CHK(st.alloc(sizeof(gpc_score) * (size_t)K));
   for (int p0 = 0; p0 < npairs; p0 += K) {
     const int pc = npairs - p0 < K ? npairs - p0 : K;
-    size_t first[5], cnt[5];
-    for (int k = 0; k < 5; ++k) first[k] = (size_t)p0, cnt[k] = (size_t)pc;
-    CHK(score_upload(c, planes, first, cnt, off, 5));
-    const uint8_t* d = (const uint8_t*)c->sc_in.p;
-    const gpc_truth dt = {(const float*)(d + off[2]), corr ? (const float*)(d + off[3]) : nullptr, truth->ignore ? d + off[4] : nullptr};
-    CHK(score_records(c, d + off[0], corr, cap, (const int32_t*)(d + off[1]), W, H, pc, &dt, t, (gpc_score*)c->sc_out.p));
-    CHK(score_download(c, scores + p0, pc));
+    // (whole, not by up_records: beside the truth planes the records are the lesser part, and per pair they went up no faster)
+    CHK(st.up(r_rec, (const uint8_t*)rec + esz * (size_t)cap * p0, esz * (size_t)cap * pc));
+    CHK(st.up(r_cnt, counts + p0, sizeof(int32_t) * (size_t)pc));
+    CHK(st.up(r_u, truth->u + n * p0, sizeof(float) * n * pc));
+    if (corr) CHK(st.up(r_v, truth->v + n * p0, sizeof(float) * n * pc));
+    if (truth->ignore) CHK(st.up(r_ign, truth->ignore + n * p0, n * pc));
+    const gpc_truth dt = {(const float*)st.p(r_u), corr ? (const float*)st.p(r_v) : nullptr, truth->ignore ? st.p(r_ign) : nullptr};
+    CHK(score_records(c, st.p(r_rec), corr, cap, (const int32_t*)st.p(r_cnt), W, H, pc, &dt, t, (gpc_score*)st.p(r_sc)));
+    CHK(score_down(st, r_sc, scores + p0, pc));
   }
   return GPC_OK;
 }
@@ -3539,66 +3600,48 @@ int gpc_hip_score_correspondences(gpc_hip_ctx* c, const gpc_correspondence* corr
   return score_records_host(c, corr, true, cap_per_pair, counts, W, H, npairs, truth, thr, n_thr, scores);
 }
 
+// images and truth of a chunk of pairs through score_match; b null: a holds npairs + 1 frames, and chunks share a frame
+static int score_match_host(gpc_hip_ctx* c, const uint8_t* a, const uint8_t* b, int W, int H, int npairs, const gpc_settings* s,
+                            const gpc_truth* truth, const float* thr, int n_thr, gpc_score* scores) {
+  const bool seq = !b;
+  CHK(truth_ok(truth, seq));
+  gpc::ScoreThr t;
+  CHK(score_thresholds(thr, n_thr, t));
+  CHK(match_usable(c, s, W, H, seq));
+  CHK(host_call_begin(c));
+  const size_t n = (size_t)W * H;
+  // pairs per chunk: 16, or the pairs of 16 frames (GPC_HIP_SEQ_FRAMES: tests)
+  const int most = seq ? (c->seq_frames > 1 && c->seq_frames < 16 ? c->seq_frames : 16) - 1 : 16;
+  const int K = npairs < most ? npairs : most;
+  Stage st(c);
+  const size_t r_a = st.in(n * (K + seq)), r_b = st.in(seq ? 0 : n * K), r_u = st.in(sizeof(float) * n * K);
+  const size_t r_v = st.in(seq ? sizeof(float) * n * K : 0), r_ign = st.in(truth->ignore ? n * K : 0);
+  const size_t r_sc = st.out(sizeof(gpc_score) * (size_t)K);
+  CHK(st.alloc(sizeof(gpc_score) * (size_t)K));
+  for (int p0 = 0; p0 < npairs; p0 += K) {
+    const int pc = npairs - p0 < K ? npairs - p0 : K;
+    CHK(st.up(r_a, a + n * p0, n * (pc + seq)));
+    if (!seq) CHK(st.up(r_b, b + n * p0, n * pc));
+    CHK(st.up(r_u, truth->u + n * p0, sizeof(float) * n * pc));
+    if (seq) CHK(st.up(r_v, truth->v + n * p0, sizeof(float) * n * pc));
+    if (truth->ignore) CHK(st.up(r_ign, truth->ignore + n * p0, n * pc));
+    const gpc_truth dt = {(const float*)st.p(r_u), seq ? (const float*)st.p(r_v) : nullptr, truth->ignore ? st.p(r_ign) : nullptr};
+    CHK(score_match(c, st.p(r_a), seq ? nullptr : st.p(r_b), W, H, pc, s, &dt, thr, n_thr, (gpc_score*)st.p(r_sc)));
+    CHK(score_down(st, r_sc, scores + p0, pc));
+  }
+  return GPC_OK;
+}
+
 int gpc_hip_score_batch(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, int W, int H, int npairs, const gpc_settings* s,
                         const gpc_truth* truth, const float* thr, int n_thr, gpc_score* scores) {
   if (!c || !rawL || !rawR || !scores || npairs <= 0) return GPC_E_INVALID;
-  CHK(truth_ok(truth, false));
-  gpc::ScoreThr t;
-  CHK(score_thresholds(thr, n_thr, t));
-  CHK(check_settings(s));
-  CHK(check_dims(W, H));
-  CHK(forest_matches(c, W, H));
-  if (c->ngroups > 1 && s->use_hashtable) return GPC_E_UNSUPPORTED;
-  CHK(score_host_begin(c));
-  const size_t n = (size_t)W * H;
-  const int K = npairs < 16 ? npairs : 16;
-  const size_t off[4] = {0, n * K, 2 * n * K, 2 * n * K + sizeof(float) * n * K};
-  CHK(ensure(c, c->sc_in, off[3] + n * K));
-  CHK(ensure(c, c->sc_out, sizeof(gpc_score) * (size_t)K));
-  const ScorePlane planes[4] = {{rawL, n}, {rawR, n}, {(const uint8_t*)truth->u, sizeof(float) * n}, {truth->ignore, n}};
-  for (int p0 = 0; p0 < npairs; p0 += K) {
-    const int pc = npairs - p0 < K ? npairs - p0 : K;
-    const size_t first[4] = {(size_t)p0, (size_t)p0, (size_t)p0, (size_t)p0}, cnt[4] = {(size_t)pc, (size_t)pc, (size_t)pc, (size_t)pc};
-    CHK(score_upload(c, planes, first, cnt, off, 4));
-    const uint8_t* d = (const uint8_t*)c->sc_in.p;
-    const gpc_truth dt = {(const float*)(d + off[2]), nullptr, truth->ignore ? d + off[3] : nullptr};
-    CHK(gpc_hip_score_batch_device(c, d + off[0], d + off[1], W, H, pc, s, &dt, thr, n_thr, (gpc_score*)c->sc_out.p));
-    CHK(score_download(c, scores + p0, pc));
-  }
-  return GPC_OK;
+  return score_match_host(c, rawL, rawR, W, H, npairs, s, truth, thr, n_thr, scores);
 }
 
 int gpc_hip_score_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, int nframes, const gpc_settings* s,
                            const gpc_truth* truth, const float* thr, int n_thr, gpc_score* scores) {
   if (!c || !frames || !scores || nframes < 2) return GPC_E_INVALID;
-  CHK(truth_ok(truth, true));
-  gpc::ScoreThr t;
-  CHK(score_thresholds(thr, n_thr, t));
-  CHK(check_settings(s));
-  CHK(check_dims(W, H));
-  CHK(forest_matches(c, W, H));
-  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
-  CHK(score_host_begin(c));
-  const size_t n = (size_t)W * H;
-  const int npairs = nframes - 1;
-  const int K = c->seq_frames > 1 && c->seq_frames < 16 ? c->seq_frames : 16;  // frames per chunk (GPC_HIP_SEQ_FRAMES: tests)
-  const int kf = nframes < K ? nframes : K, step = kf - 1;                    // (consecutive chunks share a frame)
-  const size_t pl = sizeof(float) * n * (kf - 1);
-  const size_t off[4] = {0, pad16(n * kf), pad16(n * kf) + pl, pad16(n * kf) + 2 * pl};
-  CHK(ensure(c, c->sc_in, off[3] + n * (kf - 1)));
-  CHK(ensure(c, c->sc_out, sizeof(gpc_score) * (size_t)(kf - 1)));
-  const ScorePlane planes[4] = {{frames, n}, {(const uint8_t*)truth->u, sizeof(float) * n}, {(const uint8_t*)truth->v, sizeof(float) * n},
-                                {truth->ignore, n}};
-  for (int p0 = 0; p0 < npairs; p0 += step) {
-    const int pc = npairs - p0 < step ? npairs - p0 : step;
-    const size_t first[4] = {(size_t)p0, (size_t)p0, (size_t)p0, (size_t)p0}, cnt[4] = {(size_t)pc + 1, (size_t)pc, (size_t)pc, (size_t)pc};
-    CHK(score_upload(c, planes, first, cnt, off, 4));
-    const uint8_t* d = (const uint8_t*)c->sc_in.p;
-    const gpc_truth dt = {(const float*)(d + off[1]), (const float*)(d + off[2]), truth->ignore ? d + off[3] : nullptr};
-    CHK(gpc_hip_score_sequence_device(c, d + off[0], W, H, pc + 1, s, &dt, thr, n_thr, (gpc_score*)c->sc_out.p));
-    CHK(score_download(c, scores + p0, pc));
-  }
-  return GPC_OK;
+  return score_match_host(c, frames, nullptr, W, H, nframes - 1, s, truth, thr, n_thr, scores);
 }
 
 // ------------------------------------------------------------------ point tracks over a frame sequence
@@ -3683,96 +3726,65 @@ int gpc_hip_track_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W
   return track_link(c, d_corr, cap_per_pair, d_counts, W, H, nframes - 1, d_next, d_track_id, d_tracks, track_cap, d_ntracks);
 }
 
-// Host forms.  Everything of the call is staged in ONE device block (c->tr_stage) and the device form runs once over it.
-// Pageable input passes through the page-locked arena in pieces of at most 32 MiB, page-locked input is read where it lies.
-static int track_upload(gpc_hip_ctx* c, void* d_dst, const void* src, size_t bytes) {
-  if (!bytes) return GPC_OK;
-  if (device_view_of_host(src)) {
-    HIPCHK(c, hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-    return GPC_OK;
-  }
-  const size_t piece = (size_t)32 << 20;
-  uint8_t* d_arena = nullptr;
-  CHK(xfer_reserve(c, bytes < piece ? bytes : piece, &d_arena));
-  CHK(ensure_pool(c));
-  for (size_t at = 0; at < bytes; at += piece) {
-    const size_t nb = bytes - at < piece ? bytes - at : piece;
-    host_copy(c, c->h_xfer, (const uint8_t*)src + at, nb, true);
-    host_copy_wait(c);
-    HIPCHK(c, hipMemcpyAsync((uint8_t*)d_dst + at, c->h_xfer, nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // (the arena is written again by the next piece)
-  }
-  return GPC_OK;
-}
-
+// Host forms (Stage): the whole call in one block, the device form once over it.
 namespace {
-struct TrackStage {  // offsets into c->tr_stage
-  size_t in, corr, counts, ncand, next, id, tracks, ntracks, bytes;
+struct TrackRegions {
+  size_t in, corr, cnt, nc, next, id, tab, nt;
 };
-TrackStage track_stage(size_t in_bytes, int P, int cap, int track_cap) {
-  TrackStage o;
-  const size_t rec = (size_t)P * cap;
-  o.in = 0;
-  o.corr = pad16(in_bytes);
-  o.counts = o.corr + sizeof(gpc_correspondence) * rec;
-  o.ncand = o.counts + pad16(sizeof(int32_t) * (size_t)P);
-  o.next = o.ncand + pad16(sizeof(int32_t) * (size_t)(P + 1));
-  o.id = o.next + pad16(sizeof(int32_t) * rec);
-  o.tracks = o.id + pad16(sizeof(int32_t) * rec);
-  o.ntracks = o.tracks + sizeof(gpc_track) * (size_t)track_cap;
-  o.bytes = o.ntracks + 16;
-  return o;
-}
 }  // namespace
 
-// counts (and candidate counts) first, then what they say is valid: m_t records, links and ids per pair, min(n, track_cap) rows
-static int track_download(gpc_hip_ctx* c, const TrackStage& o, int P, int cap, int track_cap, gpc_correspondence* corr,
-                          int32_t* counts, int32_t* ncand, int32_t* next, int32_t* track_id, gpc_track* tracks, int32_t* ntracks) {
-  const uint8_t* d = (const uint8_t*)c->tr_stage.p;
-  CHK(pinned_counts(c, P + 2));  // (3 words per pair: counts [P], candidates [P + 1], the number of tracks)
-  int32_t* hc = c->h_cnt;
-  HIPCHK(c, hipMemcpyAsync(hc, d + o.counts, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, c->stream));
-  if (ncand) HIPCHK(c, hipMemcpyAsync(hc + P, d + o.ncand, sizeof(int32_t) * (size_t)(P + 1), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(hc + 2 * P + 1, d + o.ntracks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+// frame_bytes: the frames of the sequence form, whose records and counts come down; 0: the records form, where they go up
+static int track_layout(Stage& st, size_t frame_bytes, int P, int cap, int track_cap, TrackRegions* r) {
+  const size_t rec = (size_t)P * cap;
+  r->in = st.in(frame_bytes);
+  r->corr = frame_bytes ? st.out(sizeof(gpc_correspondence) * rec) : st.in(sizeof(gpc_correspondence) * rec);
+  r->cnt = frame_bytes ? st.out(sizeof(int32_t) * (size_t)P) : st.in(sizeof(int32_t) * (size_t)P);
+  r->nc = st.out(sizeof(int32_t) * (size_t)(P + 1)), r->next = st.out(sizeof(int32_t) * rec), r->id = st.out(sizeof(int32_t) * rec);
+  r->tab = st.out(sizeof(gpc_track) * (size_t)track_cap), r->nt = st.out(sizeof(int32_t));
+  return st.alloc(sizeof(int32_t) * (2 * (size_t)P + 2));  // counts [P], candidates [P + 1], the number of tracks
+}
+
+// counts (and candidate counts) first, then what they say is valid: m_t records, links and ids per pair, min(n, track_cap)
+// rows.  corr, counts, ncand: null where the form does not hand them back
+static int track_down(Stage& st, const TrackRegions& r, int P, int cap, int track_cap, gpc_correspondence* corr, int32_t* counts,
+                      int32_t* ncand, int32_t* next, int32_t* track_id, gpc_track* tracks, int32_t* ntracks) {
+  int32_t* hc = st.c->h_cnt;
+  CHK(st.down(hc, r.cnt, sizeof(int32_t) * (size_t)P));
+  if (ncand) CHK(st.down(hc + P, r.nc, sizeof(int32_t) * (size_t)(P + 1)));
+  CHK(st.down(hc + 2 * P + 1, r.nt, sizeof(int32_t)));
+  CHK(st.wait());
   int status = GPC_OK;
   for (int t = 0; t < P; ++t) {
-    const int m = hc[t] < 0 ? 0 : (hc[t] > cap ? cap : hc[t]);
+    const size_t m = (size_t)valid_records(hc[t], cap), at = (size_t)t * cap;
     if (hc[t] > cap) status = GPC_E_CAPACITY;
     if (!m) continue;
-    const size_t at = (size_t)t * cap;
-    if (corr) HIPCHK(c, hipMemcpyAsync(corr + at, d + o.corr + sizeof(gpc_correspondence) * at, sizeof(gpc_correspondence) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(next + at, d + o.next + sizeof(int32_t) * at, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(track_id + at, d + o.id + sizeof(int32_t) * at, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    if (corr) CHK(st.down(corr + at, r.corr + sizeof(gpc_correspondence) * at, sizeof(gpc_correspondence) * m));
+    CHK(st.down(next + at, r.next + sizeof(int32_t) * at, sizeof(int32_t) * m));
+    CHK(st.down(track_id + at, r.id + sizeof(int32_t) * at, sizeof(int32_t) * m));
   }
-  const int n = hc[2 * P + 1];
-  if (n > track_cap) status = GPC_E_CAPACITY;
-  const int rows = n < track_cap ? n : track_cap;
-  if (rows > 0) HIPCHK(c, hipMemcpyAsync(tracks, d + o.tracks, sizeof(gpc_track) * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int nt = hc[2 * P + 1];
+  if (nt > track_cap) status = GPC_E_CAPACITY;
+  if (nt > 0 && track_cap > 0) CHK(st.down(tracks, r.tab, sizeof(gpc_track) * (size_t)(nt < track_cap ? nt : track_cap)));
+  CHK(st.wait());
   if (counts) memcpy(counts, hc, sizeof(int32_t) * (size_t)P);
   if (ncand) memcpy(ncand, hc + P, sizeof(int32_t) * (size_t)(P + 1));
-  *ntracks = n;
-  CHK(check_join_err(c));
+  *ntracks = nt;
+  CHK(check_join_err(st.c));
   return status;
 }
 
 int gpc_hip_track_records(gpc_hip_ctx* c, const gpc_correspondence* corr, int cap, const int32_t* counts, int W, int H, int npairs,
                           int32_t* next, int32_t* track_id, gpc_track* tracks, int track_cap, int32_t* ntracks) {
   CHK(track_args(c, corr, cap, counts, W, H, npairs, next, track_id, tracks, track_cap, ntracks));
-  CHK(score_host_begin(c));
-  const TrackStage o = track_stage(0, npairs, cap, track_cap);
-  CHK(ensure(c, c->tr_stage, o.bytes));
-  uint8_t* d = (uint8_t*)c->tr_stage.p;
-  CHK(track_upload(c, d + o.counts, counts, sizeof(int32_t) * (size_t)npairs));
-  for (int t = 0; t < npairs; ++t) {  // (what lies beyond a pair's count is never read, so it does not travel)
-    const int m = counts[t] < 0 ? 0 : (counts[t] > cap ? cap : counts[t]);
-    const size_t at = sizeof(gpc_correspondence) * (size_t)t * cap;
-    CHK(track_upload(c, d + o.corr + at, corr + (size_t)t * cap, sizeof(gpc_correspondence) * (size_t)m));
-  }
-  CHK(track_link(c, (const gpc_correspondence*)(d + o.corr), cap, (const int32_t*)(d + o.counts), W, H, npairs,
-                 (int32_t*)(d + o.next), (int32_t*)(d + o.id), (gpc_track*)(d + o.tracks), track_cap, (int32_t*)(d + o.ntracks)));
-  return track_download(c, o, npairs, cap, track_cap, nullptr, nullptr, nullptr, next, track_id, tracks, ntracks);
+  CHK(host_call_begin(c));
+  Stage st(c);
+  TrackRegions r;
+  CHK(track_layout(st, 0, npairs, cap, track_cap, &r));
+  CHK(st.up(r.cnt, counts, sizeof(int32_t) * (size_t)npairs));
+  CHK(st.up_records(r.corr, corr, sizeof(gpc_correspondence), cap, counts, 0, npairs));
+  CHK(track_link(c, (const gpc_correspondence*)st.p(r.corr), cap, (const int32_t*)st.p(r.cnt), W, H, npairs, (int32_t*)st.p(r.next),
+                 (int32_t*)st.p(r.id), (gpc_track*)st.p(r.tab), track_cap, (int32_t*)st.p(r.nt)));
+  return track_down(st, r, npairs, cap, track_cap, nullptr, nullptr, nullptr, next, track_id, tracks, ntracks);
 }
 
 int gpc_hip_track_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, int nframes, const gpc_settings* s,
@@ -3781,20 +3793,17 @@ int gpc_hip_track_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, 
   if (!c || !frames || nframes < 2) return GPC_E_INVALID;
   const int npairs = nframes - 1;
   CHK(track_args(c, corr, cap, counts, W, H, npairs, next, track_id, tracks, track_cap, ntracks));
-  CHK(check_settings(s));
-  CHK(check_dims(W, H));
-  CHK(forest_matches(c, W, H));
-  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
-  CHK(score_host_begin(c));
+  CHK(match_usable(c, s, W, H, true));
+  CHK(host_call_begin(c));
   const size_t n = (size_t)W * H;
-  const TrackStage o = track_stage(n * nframes, npairs, cap, track_cap);
-  CHK(ensure(c, c->tr_stage, o.bytes));
-  uint8_t* d = (uint8_t*)c->tr_stage.p;
-  CHK(track_upload(c, d + o.in, frames, n * nframes));
-  CHK(gpc_hip_track_sequence_device(c, d + o.in, W, H, nframes, s, (gpc_correspondence*)(d + o.corr), cap, (int32_t*)(d + o.counts),
-                                    (int32_t*)(d + o.ncand), (int32_t*)(d + o.next), (int32_t*)(d + o.id),
-                                    (gpc_track*)(d + o.tracks), track_cap, (int32_t*)(d + o.ntracks)));
-  return track_download(c, o, npairs, cap, track_cap, corr, counts, ncand, next, track_id, tracks, ntracks);
+  Stage st(c);
+  TrackRegions r;
+  CHK(track_layout(st, n * nframes, npairs, cap, track_cap, &r));
+  CHK(st.up(r.in, frames, n * nframes));
+  CHK(gpc_hip_track_sequence_device(c, st.p(r.in), W, H, nframes, s, (gpc_correspondence*)st.p(r.corr), cap, (int32_t*)st.p(r.cnt),
+                                    (int32_t*)st.p(r.nc), (int32_t*)st.p(r.next), (int32_t*)st.p(r.id), (gpc_track*)st.p(r.tab),
+                                    track_cap, (int32_t*)st.p(r.nt)));
+  return track_down(st, r, npairs, cap, track_cap, corr, counts, ncand, next, track_id, tracks, ntracks);
 }
 
 // ------------------------------------------------------------------ match filtering: grid motion consensus
@@ -3937,105 +3946,66 @@ int gpc_hip_consensus_correspondences_device(gpc_hip_ctx* c, const gpc_correspon
   return cons_filter<true>(c, d_rec, cap_per_pair, d_counts, W, H, npairs, prm, d_keep, d_out, cap_out, d_index, d_out_counts);
 }
 
+// match and filter, images as all_records takes them
+static int cons_match(gpc_hip_ctx* c, const uint8_t* d_a, const uint8_t* d_b, int W, int H, int npairs, const gpc_settings* s,
+                      const gpc_consensus* prm, void* d_out, int cap_out, int32_t* d_out_counts, int32_t* d_raw_counts,
+                      int32_t* d_ncand) {
+  CHK(cons_params(prm));
+  AllRecords r;
+  CHK(all_records_cap(c, s, W, H, !d_b, &r.cap));
+  CHK(cons_limits(r.cap, W, H, npairs, prm->cell));  // (before any workspace is made, too)
+  CHK(all_records(c, d_a, d_b, W, H, npairs, s, d_ncand, &r));
+  if (d_raw_counts)
+    HIPCHK(c, hipMemcpyAsync(d_raw_counts, r.counts, sizeof(int32_t) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
+  return d_b ? cons_filter<false>(c, r.rec, r.cap, r.counts, W, H, npairs, prm, nullptr, d_out, cap_out, nullptr, d_out_counts)
+             : cons_filter<true>(c, r.rec, r.cap, r.counts, W, H, npairs, prm, nullptr, d_out, cap_out, nullptr, d_out_counts);
+}
+
 int gpc_hip_consensus_batch_device(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H, int npairs,
                                    const gpc_settings* s, const gpc_consensus* prm, gpc_support* d_out, int cap_out,
                                    int32_t* d_out_counts, int32_t* d_raw_counts, int32_t* d_ncand) {
   if (!c || !d_rawL || !d_rawR || !d_out || !d_out_counts || npairs <= 0 || cap_out <= 0) return GPC_E_INVALID;
-  CHK(cons_params(prm));
-  CHK(check_settings(s));
-  CHK(check_dims(W, H));
-  CHK(forest_matches(c, W, H));
-  const int G = c->ngroups > 1 ? c->ngroups : 1;
-  if (G > 1 && s->use_hashtable) return GPC_E_UNSUPPORTED;  // (as gpc_hip_match_batch_device, before any workspace is made)
-  // every record of every pair, as gpc_hip_score_batch_device keeps them
-  const long cap = (long)G * (W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;
-  CHK(cons_limits(cap, W, H, npairs, prm->cell));
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->pipeline > 1) CHK(drain_lanes(c));
-  CHK(ensure(c, c->sc_rec, sizeof(gpc_support) * (size_t)cap * npairs));
-  CHK(ensure(c, c->sc_cnt, sizeof(int32_t) * (size_t)npairs));
-  {
-    StrictScope strict(c);
-    CHK(gpc_hip_match_batch_device(c, d_rawL, d_rawR, W, H, npairs, s, (gpc_support*)c->sc_rec.p, (int)cap, (int32_t*)c->sc_cnt.p,
-                                   d_ncand));
-  }
-  if (d_raw_counts)
-    HIPCHK(c, hipMemcpyAsync(d_raw_counts, c->sc_cnt.p, sizeof(int32_t) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
-  return cons_filter<false>(c, c->sc_rec.p, (int)cap, (const int32_t*)c->sc_cnt.p, W, H, npairs, prm, nullptr, d_out, cap_out, nullptr,
-                            d_out_counts);
+  return cons_match(c, d_rawL, d_rawR, W, H, npairs, s, prm, d_out, cap_out, d_out_counts, d_raw_counts, d_ncand);
 }
 
 int gpc_hip_consensus_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W, int H, int nframes, const gpc_settings* s,
                                       const gpc_consensus* prm, gpc_correspondence* d_out, int cap_out, int32_t* d_out_counts,
                                       int32_t* d_raw_counts, int32_t* d_ncand) {
   if (!c || !d_frames || !d_out || !d_out_counts || nframes < 2 || cap_out <= 0) return GPC_E_INVALID;
-  CHK(cons_params(prm));
-  CHK(check_settings(s));
-  CHK(check_dims(W, H));
-  CHK(forest_matches(c, W, H));
-  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
-  const int npairs = nframes - 1;
-  const long cap = (long)(W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;
-  CHK(cons_limits(cap, W, H, npairs, prm->cell));
-  HIPCHK(c, hipSetDevice(c->device));
-  CHK(ensure(c, c->sc_rec, sizeof(gpc_correspondence) * (size_t)cap * npairs));
-  CHK(ensure(c, c->sc_cnt, sizeof(int32_t) * (size_t)npairs));
-  CHK(gpc_hip_match_sequence_device(c, d_frames, W, H, nframes, s, (gpc_correspondence*)c->sc_rec.p, (int)cap, (int32_t*)c->sc_cnt.p,
-                                    d_ncand));
-  if (d_raw_counts)
-    HIPCHK(c, hipMemcpyAsync(d_raw_counts, c->sc_cnt.p, sizeof(int32_t) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
-  return cons_filter<true>(c, c->sc_rec.p, (int)cap, (const int32_t*)c->sc_cnt.p, W, H, npairs, prm, nullptr, d_out, cap_out, nullptr,
-                           d_out_counts);
+  return cons_match(c, d_frames, nullptr, W, H, nframes - 1, s, prm, d_out, cap_out, d_out_counts, d_raw_counts, d_ncand);
 }
 
-// Host forms: chunks of at most 16 pairs staged in one device block (c->cs_stage).  Of a pair only its first m_t records
-// travel up, and only what the device form writes travels down, so the caller's arrays keep every other byte.
+// Host forms (Stage): chunks of at most 16 pairs.
 extern "C++" {
 template <bool CORR>
 static int cons_host(gpc_hip_ctx* c, const void* rec, int cap, const int32_t* counts, int W, int H, int npairs,
                      const gpc_consensus* prm, uint8_t* keep, void* out, int cap_out, int32_t* index, int32_t* out_counts) {
   const size_t esz = sizeof(gpc::ConsRec<CORR>);
   CHK(cons_args(c, rec, esz, cap, counts, W, H, npairs, prm, out, cap_out, out_counts));
-  CHK(score_host_begin(c));
+  CHK(host_call_begin(c));
   const int K = npairs < 16 ? npairs : 16;
-  size_t off[7];
-  off[0] = 0;                                                    // records
-  off[1] = off[0] + pad16(esz * (size_t)cap * K);                // counts
-  off[2] = off[1] + pad16(sizeof(int32_t) * (size_t)K);          // keep
-  off[3] = off[2] + pad16((size_t)cap * K);                      // out
-  off[4] = off[3] + pad16(esz * (size_t)cap_out * K);            // index
-  off[5] = off[4] + pad16(sizeof(int32_t) * (size_t)cap_out * K);  // out_counts
-  off[6] = off[5] + pad16(sizeof(int32_t) * (size_t)K);
-  CHK(ensure(c, c->cs_stage, off[6]));
-  uint8_t* d = (uint8_t*)c->cs_stage.p;
+  Stage st(c);
+  const size_t r_rec = st.in(esz * (size_t)cap * K), r_cnt = st.in(sizeof(int32_t) * (size_t)K), r_keep = st.out((size_t)cap * K);
+  const size_t r_out = st.out(esz * (size_t)cap_out * K), r_idx = st.out(sizeof(int32_t) * (size_t)cap_out * K);
+  const size_t r_n = st.out(sizeof(int32_t) * (size_t)K);
+  CHK(st.alloc(sizeof(int32_t) * (size_t)K));
   int status = GPC_OK;
   for (int p0 = 0; p0 < npairs; p0 += K) {
     const int pc = npairs - p0 < K ? npairs - p0 : K;
-    CHK(track_upload(c, d + off[1], counts + p0, sizeof(int32_t) * (size_t)pc));
-    for (int t = 0; t < pc; ++t) {
-      const int m = counts[p0 + t] < 0 ? 0 : (counts[p0 + t] > cap ? cap : counts[p0 + t]);
-      CHK(track_upload(c, d + off[0] + esz * (size_t)t * cap, (const uint8_t*)rec + esz * (size_t)(p0 + t) * cap, esz * (size_t)m));
+    CHK(st.up(r_cnt, counts + p0, sizeof(int32_t) * (size_t)pc));
+    CHK(st.up_records(r_rec, rec, esz, cap, counts, p0, pc));
+    CHK(cons_filter<CORR>(c, st.p(r_rec), cap, (const int32_t*)st.p(r_cnt), W, H, pc, prm, keep ? st.p(r_keep) : nullptr, st.p(r_out),
+                          cap_out, index ? (int32_t*)st.p(r_idx) : nullptr, (int32_t*)st.p(r_n)));
+    CHK(st.down(c->h_cnt, r_n, sizeof(int32_t) * (size_t)pc));
+    CHK(st.wait());
+    for (int t = 0; t < pc; ++t) {  // a pair's keep bytes as far as its records go, its kept records and their indices as far as cap_out
+      const size_t m = (size_t)valid_records(counts[p0 + t], cap), w = (size_t)valid_records(c->h_cnt[t], cap_out), q = (size_t)(p0 + t);
+      if (c->h_cnt[t] > cap_out) status = GPC_E_CAPACITY;
+      if (keep && m) CHK(st.down(keep + q * cap, r_keep + (size_t)t * cap, m));
+      if (w) CHK(st.down((uint8_t*)out + esz * q * cap_out, r_out + esz * (size_t)t * cap_out, esz * w));
+      if (w && index) CHK(st.down(index + q * cap_out, r_idx + sizeof(int32_t) * (size_t)t * cap_out, sizeof(int32_t) * w));
     }
-    CHK(cons_filter<CORR>(c, d + off[0], cap, (const int32_t*)(d + off[1]), W, H, pc, prm, keep ? d + off[2] : nullptr, d + off[3],
-                          cap_out, index ? (int32_t*)(d + off[4]) : nullptr, (int32_t*)(d + off[5])));
-    CHK(pinned_counts(c, pc));
-    HIPCHK(c, hipMemcpyAsync(c->h_cnt, d + off[5], sizeof(int32_t) * (size_t)pc, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int t = 0; t < pc; ++t) {
-      const int m = counts[p0 + t] < 0 ? 0 : (counts[p0 + t] > cap ? cap : counts[p0 + t]);
-      const int n = c->h_cnt[t], w = n < cap_out ? n : cap_out;
-      if (n > cap_out) status = GPC_E_CAPACITY;
-      if (keep && m)
-        HIPCHK(c, hipMemcpyAsync(keep + (size_t)(p0 + t) * cap, d + off[2] + (size_t)t * cap, (size_t)m, hipMemcpyDeviceToHost, c->stream));
-      if (w > 0) {
-        HIPCHK(c, hipMemcpyAsync((uint8_t*)out + esz * (size_t)(p0 + t) * cap_out, d + off[3] + esz * (size_t)t * cap_out, esz * (size_t)w,
-                                 hipMemcpyDeviceToHost, c->stream));
-        if (index)
-          HIPCHK(c, hipMemcpyAsync(index + (size_t)(p0 + t) * cap_out, d + off[4] + sizeof(int32_t) * (size_t)t * cap_out,
-                                   sizeof(int32_t) * (size_t)w, hipMemcpyDeviceToHost, c->stream));
-      }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(st.wait());
     memcpy(out_counts + p0, c->h_cnt, sizeof(int32_t) * (size_t)pc);
   }
   CHK(check_join_err(c));
