@@ -654,7 +654,11 @@ int gpc_hip_reset_kernel_timing(gpc_hip_ctx* ctx);
 int gpc_hip_kernel_count(void);
 const char* gpc_hip_kernel_name(int index);
 /* The profiler's (rocprofv3) name of the template instantiation this context last launched under timing slot
- * `index`, e.g. "gpc::k_row_join<4, 256, false>"; "" before the first launch. */
+ * `index`, e.g. "gpc::k_row_join<4, 256, false>"; "" before the first launch.
+ * The slot "k_global_match" names the join launches of the last device-wide match (non-epipolar or hash table) in
+ * launch order: " + " between two launches, "[list]" behind a launch whose grid was the planner's work list, e.g.
+ * "gpc::k_row_join<8, 1024, false, true>[list] + gpc::k_row_join<4, 1024, false, true>", "gpc::k_ht_join<4, 512>";
+ * the radix-sort fallbacks read "gpc::k_g_match" and "gpc::k_ht_pairs". */
 const char* gpc_hip_kernel_launch_name(const gpc_hip_ctx* ctx, int index);
 int gpc_hip_kernel_time(gpc_hip_ctx* ctx, int index, float* total_ms, int* launches);
 

@@ -1180,9 +1180,9 @@ int plan_global(gpc_hip_ctx* c, int W, int H, int npairs, int mode, int cap, boo
     if (hashtable) {
       CHK(ensure(c, c->hkeys[i], sizeof(uint32_t) * recs));
       CHK(ensure(c, c->hvals[i], sizeof(uint32_t) * recs));
-      CHK(ensure(c, c->hrec, 2 * sizeof(uint32_t) * recs));
     }
   }
+  if (hashtable) CHK(ensure(c, c->hrec, 2 * sizeof(uint32_t) * recs));
   CHK(ensure(c, c->ghist, sizeof(int32_t) * ((size_t)256 * g.nblk + g.nmblk) * npairs));
   CHK(ensure(c, c->gmisc, sizeof(int32_t) * GM_STRIDE * npairs));
   CHK(ensure(c, c->rowcnt, sizeof(int32_t) * (size_t)H * 2 * npairs));
@@ -1214,10 +1214,177 @@ int radix_passes(gpc_hip_ctx* c, const GlobalPlan& g, int npairs, uint32_t* keys
   return GPC_OK;
 }
 
-// Non-epipolar mode: one device-wide stable radix sort per pair (k_global.h).
+// Both radix fallbacks open alike: records per row (k_g_rowcount), then every record's (code, pixel index) into keys / vals.
+void launch_radix_records(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, int npairs, const uint8_t* d_cand, uint32_t* keys,
+                          uint32_t* vals) {
+  const uint32_t* codes = (const uint32_t*)c->codes.p;
+  const uint8_t* wcand = wide_codes(c) ? d_cand : nullptr;  // 32-bit codes: 0xFFFFFFFF is told from the sentinel by the candidate byte
+  const int32_t* stats = (const int32_t*)c->stats.p;
+  const dim3 rgrid(H - 2 * GPC_R, 2, npairs);
+  hipLaunchKernelGGL(gpc::k_g_rowcount, rgrid, dim3(RM_THREADS), 0, c->stream, codes, wcand, W, H, g.rowcnt, stats, g.gmisc, g.bs);
+  hipLaunchKernelGGL(gpc::k_g_build, rgrid, dim3(RM_THREADS), 0, c->stream, codes, wcand, W, H, (const int32_t*)g.rowcnt, stats,
+                     keys, vals, g.gmisc, g.bs);
+}
+
+// launch_name[KID_GLOBAL_MATCH] names the join launches of a device-wide match in launch order (include/gpc_hip.h):
+// " + " between two launches, "[list]" behind one whose grid was the planner's work list.
+void name_join_launch(gpc_hip_ctx* c, const char* kernel, bool list) {
+  char* n = c->launch_name[KID_GLOBAL_MATCH];
+  const size_t at = strlen(n);
+  snprintf(n + at, sizeof c->launch_name[0] - at, "%s%s%s", at ? " + " : "", kernel, list ? "[list]" : "");
+}
+
+// ---------------------------------------------------------------- the two partitioned matchers' shared host side
+// Both partition the records into bins (k_gp_hist -> k_g_scan -> planner -> k_gp_scatter, k_partition.h) and join every
+// bin or run of bins in one workgroup.  The planner leaves four words for the host behind its plan: maxima over the
+// batch, copied to the page-locked c->h_flag.  What they mean is the planner's:
+struct CodeRangePlan {   // k_gp_plan (k_partition.h)
+  int32_t overflow;      // [0] a single bin beyond GpLayout::cap_hard records on a side: the caller sorts instead
+  int32_t max_parts;     // [1] largest number of partitions of a pair: the join's grid
+  int32_t max_bin_side;  // [2] largest bin, records of one side: beyond GP_NB some partitions need the 8192-record join
+  int32_t max_list;      // [3] longest list of over-large partitions of a pair: up to GP_BIGCAP it is that join's grid
+};
+struct BucketCheck {  // k_ht_check (k_htjoin.h)
+  int32_t overflow;   // [0] a bin beyond 4096 records (left + right)
+  int32_t max_bin;    // [1] largest bin, left + right records: the next attempt is sized by it
+  int32_t max_pair;   // [2] largest pair, left + right records: records per bucket
+  int32_t max_list;   // [3] longest list of bins beyond 2048 records of a pair: up to HTJ_BIGCAP the 1024-thread launch's grid
+};
+template <class Words>
+Words plan_words(const gpc_hip_ctx* c) {
+  static_assert(sizeof(Words) == 4 * sizeof(int32_t), "a planner leaves four words");
+  Words w;
+  memcpy(&w, c->h_flag, sizeof w);
+  return w;
+}
+
+// What both lay out alike: chunks of rows (L), the records, the staged matches, the landing place of the plan's words.
+struct PartIo {
+  const uint32_t* codes;
+  const uint8_t* wcand;
+  uint2* kv;
+};
+int partition_io(gpc_hip_ctx* c, const GlobalPlan& g, int H, int npairs, const uint8_t* d_cand, gpc::GpLayout& L, PartIo& io) {
+  const int rows = H - 2 * GPC_R;
+  L.rows_per_chunk = rows >= 64 ? c->rows_per_chunk : (rows + 3) / 4;  // >= 4 chunks per image
+  L.nchunk = (rows + L.rows_per_chunk - 1) / L.rows_per_chunk;
+  CHK(ensure(c, c->staged, sizeof(uint2) * (size_t)(g.nmax / 2) * npairs));  // (left, right) position per match
+  CHK(ensure(c, c->gkv, sizeof(uint2) * (size_t)g.bs.recs * npairs));
+  if (!c->h_flag) HIPCHK(c, hipHostMalloc((void**)&c->h_flag, 64, hipHostMallocDefault));
+  CHK(ensure_flag_event(c));
+  io.codes = (const uint32_t*)c->codes.p;
+  io.wcand = wide_codes(c) ? d_cand : nullptr;
+  io.kv = (uint2*)c->gkv.p;
+  return GPC_OK;
+}
+
+// k_gp_hist / k_gp_scatter come for 256, 1024 and 2048 bins
+template <bool HT>
+struct BinKernels {
+  decltype(&gpc::k_gp_hist<HT, 256>) hist;
+  decltype(&gpc::k_gp_scatter<HT, 256>) scatter;
+};
+template <bool HT>
+BinKernels<HT> bin_kernels(int nbins) {
+  const decltype(BinKernels<HT>::hist) hist[3] = {gpc::k_gp_hist<HT, 2048>, gpc::k_gp_hist<HT, 1024>, gpc::k_gp_hist<HT, 256>};
+  const decltype(BinKernels<HT>::scatter) scatter[3] = {gpc::k_gp_scatter<HT, 2048>, gpc::k_gp_scatter<HT, 1024>,
+                                                       gpc::k_gp_scatter<HT, 256>};
+  const int k = nbins > 1024 ? 0 : nbins > 256 ? 1 : 2;
+  return {hist[k], scatter[k]};
+}
+
+// One planning round: clear the plan's words (`clear`), histogram, scan, the caller's planner; the four words at d_flag
+// start for the host; scatter; wait for the words.  The scatter goes out BEFORE the host looks at them (an event marks
+// them): it does not depend on them -- only whether its result is used does -- and the device then works through the
+// host's round trip instead of idling (~15 us per call; a batch that has to be planned again, or sorted instead, has
+// scattered once for nothing).  The wait synchronises the stream once per round.
+template <bool HT, class Planner>
+int partition_round(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, int npairs, const PartIo& io, const gpc::GpLayout& L,
+                    int32_t* tabs, int32_t* d_flag, void* clear, size_t clear_bytes, Planner launch_planner) {
+  const BinKernels<HT> k = bin_kernels<HT>(L.nbins);
+  const dim3 cgrid(L.nchunk, 2, npairs);
+  {
+    Timed t(c, KID_GLOBAL_KEYS);
+    HIPCHK(c, hipMemsetAsync(clear, 0, clear_bytes, c->stream));
+    hipLaunchKernelGGL(k.hist, cgrid, dim3(GPS_THREADS), 0, c->stream, io.codes, io.wcand, W, H, g.bs.codes, tabs, L, make_divw(W));
+    hipLaunchKernelGGL(gpc::k_g_scan, dim3(1, 2 * npairs), dim3(1024), 0, c->stream, tabs, L.nbins * L.nchunk,
+                       (long)L.nbins * L.nchunk);
+    CHK(launch_planner());
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipMemcpyAsync(c->h_flag, d_flag, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipEventRecord(c->e_flag, c->stream));
+  {
+    Timed t(c, KID_GLOBAL_SORT);
+    hipLaunchKernelGGL(k.scatter, cgrid, dim3(GPS_THREADS), 0, c->stream, io.codes, io.wcand, W, H, g.bs.codes,
+                       (const int32_t*)tabs, L, make_divw(W), io.kv, g.bs.recs);
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipEventSynchronize(c->e_flag));
+  return GPC_OK;
+}
+
+// A launch for the few over-large partitions / bins on the second stream, beside the main stream's launch instead of
+// after it: the constructor forks (s_aux waits for what the main stream holds), side_done() goes behind the side launch,
+// join() behind the main one.  Not `on`: all three do nothing.
+struct SideLaunch {
+  gpc_hip_ctx* c;
+  bool on;
+  int status;  // of the fork: CHK it before the side launch
+  SideLaunch(gpc_hip_ctx* ctx, bool on_) : c(ctx), on(on_), status(on_ ? fork() : GPC_OK) {}
+  int fork() {
+    CHK(ensure_aux_stream(c));
+    HIPCHK(c, hipEventRecord(c->e_fork, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->s_aux, c->e_fork, 0));
+    return GPC_OK;
+  }
+  int side_done() {
+    if (on) HIPCHK(c, hipEventRecord(c->e_join, c->s_aux));
+    return GPC_OK;
+  }
+  int join() {
+    if (on) HIPCHK(c, hipStreamWaitEvent(c->stream, c->e_join, 0));
+    return GPC_OK;
+  }
+};
+
+// the longest work list of the batch as a launch's x dimension
+inline dim3 list_grid(int max_list, int npairs) { return dim3(max_list > 0 ? max_list : 1, npairs); }
+
+// k_row_join<SPT, 1024, WIDE, true>, one workgroup per partition.  SPT = 4: 8192 table slots for up to 4096 left records
+// (64 KiB, two workgroups = 32 waves per CU); SPT = 8: 16384 slots for up to 8192 (one workgroup per CU).
+template <int SPT>
+int launch_vjoin(gpc_hip_ctx* c, hipStream_t stream, dim3 grid, bool wide, int W, int H, const gpc_settings* s, int mode,
+                 const gpc::RjVirt& v) {
+  constexpr int log2s = SPT == 8 ? 14 : 13;
+  constexpr size_t lds = ((size_t)8 * ((1u << log2s) + 1) + 15) / 16 * 16;
+  auto launch = [&](auto kernel) -> int {
+    CHK(allow_dyn_lds(c, reinterpret_cast<const void*>(kernel), lds));
+    hipLaunchKernelGGL(kernel, grid, dim3(1024), lds, stream, (const uint32_t*)nullptr, (const uint8_t*)nullptr, W, H,
+                       s->disp_high, mode == 0 ? 1 : 0, (const int32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, log2s, 1, v);
+    return GPC_OK;
+  };
+  CHK(wide ? launch(gpc::k_row_join<SPT, 1024, true, true>) : launch(gpc::k_row_join<SPT, 1024, false, true>));
+  char name[48];
+  snprintf(name, sizeof name, "gpc::k_row_join<%d, 1024, %s, true>", SPT, wide ? "true" : "false");
+  name_join_launch(c, name, v.use_list != 0);
+  return GPC_OK;
+}
+
+// k_ht_join<RPT, NT>, one workgroup per bin of at most NT * RPT records (8 bytes of LDS each)
+template <int RPT, int NT>
+int launch_htjoin(gpc_hip_ctx* c, hipStream_t stream, dim3 grid, const gpc::HtjArgs& a) {
+  constexpr size_t lds = (size_t)8 * NT * RPT;
+  CHK(allow_dyn_lds(c, reinterpret_cast<const void*>(gpc::k_ht_join<RPT, NT>), lds));
+  hipLaunchKernelGGL((gpc::k_ht_join<RPT, NT>), grid, dim3(NT), lds, stream, a);
+  char name[32];
+  snprintf(name, sizeof name, "gpc::k_ht_join<%d, %d>", RPT, NT);
+  name_join_launch(c, name, a.use_list != 0);
+  return GPC_OK;
+}
+
 // Non-epipolar matcher by partition + LDS join (k_partition.h).  *done = false when some partition is too large for one
 // workgroup (heavily duplicated codes): nothing has been written then and the caller takes the radix-sort path.
-// The overflow word is read back, so this mode synchronises the stream once per call.
 int run_partition_match(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, int npairs, const gpc_settings* s, int mode,
                         const uint8_t* d_cand, void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand, bool* done) {
   *done = false;
@@ -1243,72 +1410,34 @@ int run_partition_match(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, int n
   // plan kernel's LDS (8 bytes per possible partition) outgrew a workgroup's 160 KiB from ~6.5 M pixels on and the
   // launch failed where the radix path would have served (3840x2160: 189 KB)
   if (L.pmax > L.nbins) L.pmax = L.nbins;
-  const int rows = H - 2 * GPC_R;
-  L.rows_per_chunk = rows >= 64 ? c->rows_per_chunk : (rows + 3) / 4;  // >= 4 chunks per image
-  L.nchunk = (rows + L.rows_per_chunk - 1) / L.rows_per_chunk;
   L.o_off = 0;
   L.o_rowcnt = L.o_off + 2 * (L.pmax + 1);
   L.o_misc = L.o_rowcnt + L.pmax;
   L.ps = L.o_misc + 8 + GP_BIGCAP;
+  PartIo io;
+  CHK(partition_io(c, g, H, npairs, d_cand, L, io));
+  // gpart: [(bin, chunk) tables][plan block per pair][the four words]
   const size_t tab_ints = (size_t)2 * npairs * L.nbins * L.nchunk;
   const size_t plan_bytes = sizeof(int32_t) * ((size_t)L.ps * npairs + 4);
   CHK(ensure(c, c->gpart, sizeof(int32_t) * tab_ints + plan_bytes));
-  CHK(ensure(c, c->staged, sizeof(uint2) * (size_t)(g.nmax / 2) * npairs));  // (left, right) pixel index per match
-  if (!c->h_flag) HIPCHK(c, hipHostMalloc((void**)&c->h_flag, 64, hipHostMallocDefault));
   int32_t* tabs = (int32_t*)c->gpart.p;
   int32_t* part = tabs + tab_ints;
   int32_t* d_flag = part + (size_t)L.ps * npairs;
-  const uint32_t* codes = (const uint32_t*)c->codes.p;
-  const uint8_t* wcand = wide ? d_cand : nullptr;
-  CHK(ensure(c, c->gkv, sizeof(uint2) * (size_t)g.bs.recs * npairs));
-  uint2* kv = (uint2*)c->gkv.p;
-  dim3 cgrid(L.nchunk, 2, npairs);
   const size_t plan_lds = sizeof(int32_t) * 2 * ((size_t)L.pmax + 1);
-  {
-    Timed t(c, KID_GLOBAL_KEYS);
-    HIPCHK(c, hipMemsetAsync(part, 0, plan_bytes, c->stream));
-    if (L.nbins > 1024)
-      hipLaunchKernelGGL((gpc::k_gp_hist<false, 2048>), cgrid, dim3(GPS_THREADS), 0, c->stream, codes, wcand, W, H, g.bs.codes,
-                         tabs, L, make_divw(W));
-    else if (L.nbins > 256)
-      hipLaunchKernelGGL((gpc::k_gp_hist<false, 1024>), cgrid, dim3(GPS_THREADS), 0, c->stream, codes, wcand, W, H, g.bs.codes,
-                         tabs, L, make_divw(W));
-    else
-      hipLaunchKernelGGL((gpc::k_gp_hist<false, 256>), cgrid, dim3(GPS_THREADS), 0, c->stream, codes, wcand, W, H, g.bs.codes,
-                         tabs, L, make_divw(W));
-    hipLaunchKernelGGL(gpc::k_g_scan, dim3(1, 2 * npairs), dim3(1024), 0, c->stream, tabs, L.nbins * L.nchunk,
-                       (long)L.nbins * L.nchunk);
+  CHK(partition_round<false>(c, g, W, H, npairs, io, L, tabs, d_flag, part, plan_bytes, [&]() -> int {
     CHK(allow_dyn_lds(c, reinterpret_cast<const void*>(gpc::k_gp_plan), plan_lds));
     hipLaunchKernelGGL(gpc::k_gp_plan, dim3(npairs), dim3(GP_THREADS), plan_lds, c->stream, (const int32_t*)tabs,
                        (const int32_t*)c->stats.p, part, L, d_flag);
-    HIPCHK(c, hipGetLastError());
-  }
-  HIPCHK(c, hipMemcpyAsync(c->h_flag, d_flag, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  // (the scatter goes out before the host looks at the plan's words, as in the hash-table matcher below: the device works
-  // through the host's round trip; a batch that is sorted instead has scattered once for nothing)
-  CHK(ensure_flag_event(c));
-  HIPCHK(c, hipEventRecord(c->e_flag, c->stream));
-  {
-    Timed t(c, KID_GLOBAL_SORT);
-    if (L.nbins > 1024)
-      hipLaunchKernelGGL((gpc::k_gp_scatter<false, 2048>), cgrid, dim3(GPS_THREADS), 0, c->stream, codes, wcand, W, H,
-                         g.bs.codes, (const int32_t*)tabs, L, make_divw(W), kv, g.bs.recs);
-    else if (L.nbins > 256)
-      hipLaunchKernelGGL((gpc::k_gp_scatter<false, 1024>), cgrid, dim3(GPS_THREADS), 0, c->stream, codes, wcand, W, H,
-                         g.bs.codes, (const int32_t*)tabs, L, make_divw(W), kv, g.bs.recs);
-    else
-      hipLaunchKernelGGL((gpc::k_gp_scatter<false, 256>), cgrid, dim3(GPS_THREADS), 0, c->stream, codes, wcand, W, H,
-                         g.bs.codes, (const int32_t*)tabs, L, make_divw(W), kv, g.bs.recs);
-    HIPCHK(c, hipGetLastError());
-  }
-  HIPCHK(c, hipEventSynchronize(c->e_flag));
-  if (c->h_flag[0]) return GPC_OK;  // a single bin beyond 8192 records: the caller sorts instead
-  const bool big_bins = c->h_flag[2] > GP_NB;  // some partitions (single bins) need the 8192-record join
-  const int maxparts = c->h_flag[1] > 0 ? c->h_flag[1] : 1;
+    return GPC_OK;
+  }));
+  const CodeRangePlan plan = plan_words<CodeRangePlan>(c);
+  if (plan.overflow) return GPC_OK;
+  const int maxparts = plan.max_parts > 0 ? plan.max_parts : 1;
   {
     Timed t(c, KID_GLOBAL_MATCH);
+    c->launch_name[KID_GLOBAL_MATCH][0] = 0;
     gpc::RjVirt v;
-    v.kv = kv;
+    v.kv = io.kv;
     v.part = part;
     v.staged = (uint32_t*)c->staged.p;
     v.recs = g.bs.recs;
@@ -1321,48 +1450,23 @@ int run_partition_match(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, int n
     v.vtol = s->vertical_tolerance;
     v.min_recs = -1;
     v.use_list = 0;
-    // 8192 slots for up to 4096 left records: 64 KiB, two workgroups = 32 waves per CU; 16384 for up to 8192: one workgroup.
     // Every partition goes to the 4096-record launch except the bins that are larger by themselves: those few (19 of
-    // 1024 code ranges of a 1920x1080 image with the Tau forest) get a launch of the 8192-record instantiation, in which
-    // all other workgroups return at once.  (Planning the whole batch for the larger kernel, as before, ran every
+    // 1024 code ranges of a 1920x1080 image with the Tau forest) get a launch of the 8192-record instantiation first, on
+    // the second stream: its workgroups (one per CU, 44-48 us per 8 pairs of 1920x1080 as a launch by itself) run beside
+    // the 4096-record launch instead of after it.  (Planning the whole batch for the larger kernel, as before, ran every
     // partition at one workgroup per CU.)
-    int log2s = 13;
-    size_t lds = ((size_t)8 * ((1u << log2s) + 1) + 15) / 16 * 16;
-    const int apply_filter = (mode == 0);
     const dim3 jgrid(maxparts, npairs);
-    dim3 jgrid_(jgrid);
-#define LAUNCH_VJOIN(SPT, WIDE, STREAM)                                                                                 \
-  do {                                                                                                                  \
-    const void* fn_ = reinterpret_cast<const void*>(gpc::k_row_join<SPT, 1024, WIDE, true>);                            \
-    CHK(allow_dyn_lds(c, fn_, lds));                                                                                    \
-    hipLaunchKernelGGL((gpc::k_row_join<SPT, 1024, WIDE, true>), jgrid_, dim3(1024), lds, STREAM, (const uint32_t*)nullptr, \
-                       (const uint8_t*)nullptr, W, H, s->disp_high, apply_filter, (const int32_t*)nullptr,              \
-                       (uint32_t*)nullptr, (int32_t*)nullptr, log2s, 1, v);                                             \
-  } while (0)
-    if (big_bins) {
-      // The few over-large partitions first, on a stream of their own: their 8192-record workgroups (one per CU, 44-48 us
-      // per 8 pairs of 1920x1080 as a launch by itself) run beside the 4096-record launch instead of after it.
-      CHK(ensure_aux_stream(c));
-      HIPCHK(c, hipEventRecord(c->e_fork, c->stream));
-      HIPCHK(c, hipStreamWaitEvent(c->s_aux, c->e_fork, 0));
-      gpc::RjVirt v4 = v;
-      v.min_recs = GP_NB;
-      if (c->h_flag[3] <= GP_BIGCAP) {  // the plan's work list is the grid
-        v.use_list = 1;
-        jgrid_ = dim3(c->h_flag[3] > 0 ? c->h_flag[3] : 1, npairs);
-      }
-      log2s = 14;
-      lds = ((size_t)8 * ((1u << log2s) + 1) + 15) / 16 * 16;
-      if (wide) LAUNCH_VJOIN(8, true, c->s_aux); else LAUNCH_VJOIN(8, false, c->s_aux);
-      HIPCHK(c, hipEventRecord(c->e_join, c->s_aux));
-      v = v4;
-      jgrid_ = jgrid;
-      log2s = 13;
-      lds = ((size_t)8 * ((1u << log2s) + 1) + 15) / 16 * 16;
+    SideLaunch side(c, plan.max_bin_side > GP_NB);
+    CHK(side.status);
+    if (side.on) {
+      gpc::RjVirt big = v;
+      big.min_recs = GP_NB;
+      big.use_list = plan.max_list <= GP_BIGCAP;  // the plan's work list is the grid; else every partition, nearly all returning at once
+      CHK(launch_vjoin<8>(c, c->s_aux, big.use_list ? list_grid(plan.max_list, npairs) : jgrid, wide, W, H, s, mode, big));
+      CHK(side.side_done());
     }
-    if (wide) LAUNCH_VJOIN(4, true, c->stream); else LAUNCH_VJOIN(4, false, c->stream);
-    if (big_bins) HIPCHK(c, hipStreamWaitEvent(c->stream, c->e_join, 0));
-#undef LAUNCH_VJOIN
+    CHK(launch_vjoin<4>(c, c->stream, jgrid, wide, W, H, s, mode, v));
+    CHK(side.join());
     hipLaunchKernelGGL(gpc::k_gp_gather, dim3((maxparts + GPG_PARTS - 1) / GPG_PARTS, npairs), dim3(RM_THREADS), 0, c->stream,
                        (const uint32_t*)c->staged.p, (const int32_t*)part, L, g.bs.recs, make_divw(W),
                        mode, d_out, g.bs.out, cap, d_counts, (const int32_t*)c->stats.p, d_ncand);
@@ -1372,6 +1476,7 @@ int run_partition_match(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, int n
   return GPC_OK;
 }
 
+// Non-epipolar mode: the partitioned matcher, or one device-wide stable radix sort per pair (k_global.h).
 int run_global_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, int mode, const uint8_t* d_cand,
                      void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand, bool seq) {
   GlobalPlan g;
@@ -1382,18 +1487,12 @@ int run_global_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_setting
     if (done) return GPC_OK;
   }
   const int apply_filter = (mode == 0);
-  const uint32_t* codes = (const uint32_t*)c->codes.p;
-  const uint8_t* wcand = wide_codes(c) ? d_cand : nullptr;  // 32-bit codes: 0xFFFFFFFF is told from the sentinel by the candidate byte
   const int32_t* stats = (const int32_t*)c->stats.p;
   uint32_t* keys[2] = {(uint32_t*)c->gkeys[0].p, (uint32_t*)c->gkeys[1].p};
   uint32_t* vals[2] = {(uint32_t*)c->gvals[0].p, (uint32_t*)c->gvals[1].p};
-  dim3 rgrid(H - 2 * GPC_R, 2, npairs);
   {
     Timed t(c, KID_GLOBAL_KEYS);
-    hipLaunchKernelGGL(gpc::k_g_rowcount, rgrid, dim3(RM_THREADS), 0, c->stream, codes, wcand, W, H, g.rowcnt, stats,
-                       g.gmisc, g.bs);
-    hipLaunchKernelGGL(gpc::k_g_build, rgrid, dim3(RM_THREADS), 0, c->stream, codes, wcand, W, H,
-                       (const int32_t*)g.rowcnt, stats, keys[0], vals[0], g.gmisc, g.bs);
+    launch_radix_records(c, g, W, H, npairs, d_cand, keys[0], vals[0]);
     HIPCHK(c, hipGetLastError());
   }
   {
@@ -1402,6 +1501,8 @@ int run_global_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_setting
   }
   {
     Timed t(c, KID_GLOBAL_MATCH);
+    c->launch_name[KID_GLOBAL_MATCH][0] = 0;
+    name_join_launch(c, "gpc::k_g_match", false);
     const int ngm = (g.nmax + GMT_TILE - 1) / GMT_TILE;  // <= nmblk, so the match-block counters are large enough
     hipLaunchKernelGGL((gpc::k_g_match<false>), dim3(ngm, npairs), dim3(RM_THREADS), 0, c->stream,
                        (const uint32_t*)keys[0], (const uint32_t*)vals[0], (const int32_t*)g.gmisc, make_divw(W),
@@ -1418,8 +1519,7 @@ int run_global_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_setting
 }
 
 // useHashtable mode by partition into bins of 1024 buckets + one workgroup per bin (k_htjoin.h).  *done = false when a bin
-// holds more records than one workgroup takes (the overflow word, read back after the histogram: one stream
-// synchronisation per call); nothing has been written then and the caller takes the radix path.
+// holds more records than one workgroup takes; nothing has been written then and the caller takes the radix path.
 int run_hashtable_partition(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, int npairs, const gpc_settings* s, int mode,
                             const uint8_t* d_cand, void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand, bool* done) {
   *done = false;
@@ -1438,20 +1538,14 @@ int run_hashtable_partition(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, i
   if (c->ht_lbits > 0) lbits = c->ht_lbits;
   int rpt = 4;
   L.epi = s->epipolar_mode ? 1 : 0;
-  const int rows = H - 2 * GPC_R;
-  L.rows_per_chunk = rows >= 64 ? c->rows_per_chunk : (rows + 3) / 4;
-  L.nchunk = (rows + L.rows_per_chunk - 1) / L.rows_per_chunk;
-  CHK(ensure(c, c->staged, sizeof(uint2) * (size_t)(g.nmax / 2) * npairs));
-  if (!c->h_flag) HIPCHK(c, hipHostMalloc((void**)&c->h_flag, 64, hipHostMallocDefault));
-  const uint32_t* codes = (const uint32_t*)c->codes.p;
-  const uint8_t* wcand = wide_codes(c) ? d_cand : nullptr;
-  CHK(ensure(c, c->gkv, sizeof(uint2) * (size_t)g.bs.recs * npairs));
-  uint2* kv = (uint2*)c->gkv.p;
-  dim3 cgrid(L.nchunk, 2, npairs);
+  PartIo io;
+  CHK(partition_io(c, g, H, npairs, d_cand, L, io));
   int32_t *tabs = nullptr, *bincnt = nullptr, *biglist = nullptr;
+  BucketCheck chk;
   for (int attempt = 0;; ++attempt) {
     L.bshift = lbits;
     L.nbins = (int)((HM_BUCKETS + (1u << lbits) - 1) >> lbits);  // 210 / 420 / 839 / 1678
+    // gpart: [(bin, chunk) tables][pairs per bin][the four words][work list per pair]
     const size_t tab_ints = (size_t)2 * npairs * L.nbins * L.nchunk;
     const size_t cnt_ints = (size_t)npairs * L.nbins;
     const size_t big_ints = (size_t)npairs * (HTJ_BIGCAP + 1);
@@ -1460,59 +1554,26 @@ int run_hashtable_partition(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, i
     bincnt = tabs + tab_ints;
     int32_t* d_flag = bincnt + cnt_ints;
     biglist = d_flag + 4;
-    {
-      Timed t(c, KID_GLOBAL_KEYS);
-      HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int32_t) * (4 + big_ints), c->stream));
-      if (L.nbins > 1024)
-        hipLaunchKernelGGL((gpc::k_gp_hist<true, 2048>), cgrid, dim3(GPS_THREADS), 0, c->stream, codes, wcand, W, H, g.bs.codes,
-                           tabs, L, make_divw(W));
-      else if (L.nbins > 256)
-        hipLaunchKernelGGL((gpc::k_gp_hist<true, 1024>), cgrid, dim3(GPS_THREADS), 0, c->stream, codes, wcand, W, H, g.bs.codes,
-                           tabs, L, make_divw(W));
-      else
-        hipLaunchKernelGGL((gpc::k_gp_hist<true, 256>), cgrid, dim3(GPS_THREADS), 0, c->stream, codes, wcand, W, H, g.bs.codes,
-                           tabs, L, make_divw(W));
-      hipLaunchKernelGGL(gpc::k_g_scan, dim3(1, 2 * npairs), dim3(1024), 0, c->stream, tabs, L.nbins * L.nchunk,
-                         (long)L.nbins * L.nchunk);
+    CHK(partition_round<true>(c, g, W, H, npairs, io, L, tabs, d_flag, d_flag, sizeof(int32_t) * (4 + big_ints), [&]() -> int {
       hipLaunchKernelGGL(gpc::k_ht_check, dim3(npairs), dim3(256), 0, c->stream, (const int32_t*)tabs,
                          (const int32_t*)c->stats.p, L.nbins, L.nchunk, HTJ_THREADS * 4, d_flag, 512 * 4, biglist);
-      HIPCHK(c, hipGetLastError());
-    }
-    HIPCHK(c, hipMemcpyAsync(c->h_flag, d_flag, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    // The scatter goes out BEFORE the host looks at the plan's words (an event marks them): it does not depend on them --
-    // only whether its result is used does -- and the device then works through the host's round trip instead of idling
-    // (~15 us per call; a batch that has to be planned again, or sorted instead, has scattered once for nothing).
-    CHK(ensure_flag_event(c));
-    HIPCHK(c, hipEventRecord(c->e_flag, c->stream));
-  {
-    Timed t(c, KID_GLOBAL_SORT);
-    if (L.nbins > 1024)
-      hipLaunchKernelGGL((gpc::k_gp_scatter<true, 2048>), cgrid, dim3(GPS_THREADS), 0, c->stream, codes, wcand, W, H,
-                         g.bs.codes, (const int32_t*)tabs, L, make_divw(W), kv, g.bs.recs);
-    else if (L.nbins > 256)
-      hipLaunchKernelGGL((gpc::k_gp_scatter<true, 1024>), cgrid, dim3(GPS_THREADS), 0, c->stream, codes, wcand, W, H,
-                         g.bs.codes, (const int32_t*)tabs, L, make_divw(W), kv, g.bs.recs);
-    else
-      hipLaunchKernelGGL((gpc::k_gp_scatter<true, 256>), cgrid, dim3(GPS_THREADS), 0, c->stream, codes, wcand, W, H,
-                         g.bs.codes, (const int32_t*)tabs, L, make_divw(W), kv, g.bs.recs);
-    HIPCHK(c, hipGetLastError());
-  }
-    HIPCHK(c, hipEventSynchronize(c->e_flag));
-    if (!c->h_flag[0]) {  // every bin fits the 4096-record kernel
+      return GPC_OK;
+    }));
+    chk = plan_words<BucketCheck>(c);
+    if (!chk.overflow) {  // every bin fits the 4096-record kernel
       c->ht_hint_w = W;
       c->ht_hint_h = H;
       c->ht_hint_lbits = lbits;
       break;
     }
-    const int maxbin = c->h_flag[1];
     // halving the buckets per bin halves an evenly filled bin: how many halvings bring the largest one under 3900?
     int want = lbits;
-    while (want > 7 && (maxbin >> (lbits - want)) > 3900) --want;
+    while (want > 7 && (chk.max_bin >> (lbits - want)) > 3900) --want;
     if (want < lbits && c->ht_lbits == 0 && attempt < 3) {
       lbits = want;
       continue;
     }
-    if (maxbin <= HTJ_THREADS * 8) {  // the 8192-record kernel takes what is left (one workgroup per CU)
+    if (chk.max_bin <= HTJ_THREADS * 8) {  // the 8192-record kernel takes what is left (one workgroup per CU)
       rpt = 8;
       break;
     }
@@ -1520,8 +1581,9 @@ int run_hashtable_partition(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, i
   }
   {
     Timed t(c, KID_GLOBAL_MATCH);
+    c->launch_name[KID_GLOBAL_MATCH][0] = 0;
     gpc::HtjArgs a;
-    a.kv = kv;
+    a.kv = io.kv;
     a.tabs = tabs;
     a.stats = (const int32_t*)c->stats.p;
     a.staged = (uint2*)c->staged.p;
@@ -1532,56 +1594,42 @@ int run_hashtable_partition(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, i
     a.lbits = lbits;
     // Ten-record lists that fill up (k_htjoin.h): measured per-record handling against one wave per bucket --
     // 1920x1080 x8 (13 records per bucket): k_ht_join 787 -> 527 us; 1024x436 x32 (2.7 per bucket): 239 -> 278 us.  The
-    // batch's largest record count (k_ht_check reports it with the largest bin) decides: from 8 records per bucket on.
-    a.mid = c->ht_mid > 0 ? c->ht_mid : ((double)c->h_flag[2] / (double)HM_BUCKETS >= 8.0 ? 32 : HM_CAP);
+    // batch's largest record count decides: from 8 records per bucket on.
+    a.mid = c->ht_mid > 0 ? c->ht_mid : ((double)chk.max_pair / (double)HM_BUCKETS >= 8.0 ? 32 : HM_CAP);
     a.epi = L.epi;
     a.disp_high = s->disp_high;
     a.vtol = s->vertical_tolerance;
     a.apply_filter = (mode == 0);
     a.dw = make_divw(W);
-    // 512 threads where the bins are small (k_htjoin.h): at most 512 buckets, and bins of at most 2048 records; the few
-    // larger ones (a bucket of repeated states can double a bin) go to a 1024-thread launch on a stream of its own beside it
-    const bool half = rpt == 4 && lbits <= 9 && !c->ht_no_half &&
-                      (double)c->h_flag[2] / (double)L.nbins <= 0.9 * 512 * 4;  // the average bin fits comfortably
-    const bool split = half && c->h_flag[1] > 512 * 4;
     a.min_recs = -1;
     a.use_list = 0;
     a.biglist = biglist;
+    // 512 threads where the bins are small (k_htjoin.h): at most 512 buckets, and bins of at most 2048 records; the few
+    // larger ones (a bucket of repeated states can double a bin) go to a 1024-thread launch on a stream of its own beside it
+    const bool half = rpt == 4 && lbits <= 9 && !c->ht_no_half &&
+                      (double)chk.max_pair / (double)L.nbins <= 0.9 * 512 * 4;  // the average bin fits comfortably
     if (c->debug_plan)
-      fprintf(stderr, "[ht plan] lbits %d bins %d largest bin %d largest pair %d rpt %d half %d mid %d\n", lbits, L.nbins, c->h_flag[1],
-              c->h_flag[2], rpt, (int)half, a.mid);
-    dim3 hgrid(L.nbins, npairs);
-#define LAUNCH_HTJ(RPT, NT, STREAM)                                                                                      \
-  do {                                                                                                                   \
-    const size_t lds_ = (size_t)8 * NT * RPT;                                                                            \
-    CHK(allow_dyn_lds(c, reinterpret_cast<const void*>(gpc::k_ht_join<RPT, NT>), lds_));                                 \
-    hipLaunchKernelGGL((gpc::k_ht_join<RPT, NT>), hgrid, dim3(NT), lds_, STREAM, a);                                     \
-  } while (0)
+      fprintf(stderr, "[ht plan] lbits %d bins %d largest bin %d largest pair %d rpt %d half %d mid %d\n", lbits, L.nbins, chk.max_bin,
+              chk.max_pair, rpt, (int)half, a.mid);
+    const dim3 hgrid(L.nbins, npairs);
     // (every bin is taken by exactly one launch: k_ht_check has seen that none exceeds the largest kernel's capacity)
     if (rpt == 8) {
-      LAUNCH_HTJ(8, HTJ_THREADS, c->stream);
+      CHK((launch_htjoin<8, HTJ_THREADS>(c, c->stream, hgrid, a)));
     } else if (half) {
-      if (split) {
-        CHK(ensure_aux_stream(c));
-        HIPCHK(c, hipEventRecord(c->e_fork, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->s_aux, c->e_fork, 0));
-        a.min_recs = 512 * 4;
-        if (c->h_flag[3] <= HTJ_BIGCAP) {  // the larger bins' list is the grid (else: every bin, nearly all returning at once)
-          a.use_list = 1;
-          hgrid = dim3(c->h_flag[3] > 0 ? c->h_flag[3] : 1, npairs);
-        }
-        LAUNCH_HTJ(4, HTJ_THREADS, c->s_aux);
-        HIPCHK(c, hipEventRecord(c->e_join, c->s_aux));
-        a.min_recs = -1;
-        a.use_list = 0;
-        hgrid = dim3(L.nbins, npairs);
+      SideLaunch side(c, chk.max_bin > 512 * 4);
+      CHK(side.status);
+      if (side.on) {
+        gpc::HtjArgs big = a;
+        big.min_recs = 512 * 4;
+        big.use_list = chk.max_list <= HTJ_BIGCAP;  // the larger bins' list is the grid; else every bin, nearly all returning at once
+        CHK((launch_htjoin<4, HTJ_THREADS>(c, c->s_aux, big.use_list ? list_grid(chk.max_list, npairs) : hgrid, big)));
+        CHK(side.side_done());
       }
-      LAUNCH_HTJ(4, 512, c->stream);
-      if (split) HIPCHK(c, hipStreamWaitEvent(c->stream, c->e_join, 0));
+      CHK((launch_htjoin<4, 512>(c, c->stream, hgrid, a)));
+      CHK(side.join());
     } else {
-      LAUNCH_HTJ(4, HTJ_THREADS, c->stream);
+      CHK((launch_htjoin<4, HTJ_THREADS>(c, c->stream, hgrid, a)));
     }
-#undef LAUNCH_HTJ
     hipLaunchKernelGGL(gpc::k_ht_gather, dim3((L.nbins + HTG_BINS - 1) / HTG_BINS, npairs), dim3(RM_THREADS), 0, c->stream, a,
                        mode, d_out, g.bs.out, cap, d_counts, d_ncand);
     HIPCHK(c, hipGetLastError());
@@ -1590,7 +1638,8 @@ int run_hashtable_partition(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, i
   return GPC_OK;
 }
 
-// useHashtable mode (hashmatch.hpp): stable radix sort by bucket id + one thread per bucket (k_hashtable.h)
+// useHashtable mode (hashmatch.hpp): the partitioned matcher, or a stable radix sort by bucket id + one thread per bucket
+// (k_hashtable.h)
 int run_hashtable_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, int mode, const uint8_t* d_cand,
                         void* d_out, int cap, int32_t* d_counts, int32_t* d_ncand, bool seq) {
   GlobalPlan g;
@@ -1602,20 +1651,14 @@ int run_hashtable_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_sett
   }
   const int apply_filter = (mode == 0);
   const int epi = s->epipolar_mode ? 1 : 0;
-  const uint32_t* codes = (const uint32_t*)c->codes.p;
-  const uint8_t* wcand = wide_codes(c) ? d_cand : nullptr;
   const int32_t* stats = (const int32_t*)c->stats.p;
   uint32_t* codes0 = (uint32_t*)c->gkeys[0].p;
   uint32_t* kv0 = (uint32_t*)c->gvals[0].p;
   uint32_t* keys[2] = {(uint32_t*)c->hkeys[0].p, (uint32_t*)c->hkeys[1].p};
   uint32_t* vals[2] = {(uint32_t*)c->hvals[0].p, (uint32_t*)c->hvals[1].p};
-  dim3 rgrid(H - 2 * GPC_R, 2, npairs);
   {
     Timed t(c, KID_GLOBAL_KEYS);
-    hipLaunchKernelGGL(gpc::k_g_rowcount, rgrid, dim3(RM_THREADS), 0, c->stream, codes, wcand, W, H, g.rowcnt, stats,
-                       g.gmisc, g.bs);
-    hipLaunchKernelGGL(gpc::k_g_build, rgrid, dim3(RM_THREADS), 0, c->stream, codes, wcand, W, H,
-                       (const int32_t*)g.rowcnt, stats, codes0, kv0, g.gmisc, g.bs);
+    launch_radix_records(c, g, W, H, npairs, d_cand, codes0, kv0);
     hipLaunchKernelGGL(gpc::k_ht_bucket_ids, dim3(g.nmblk, npairs), dim3(256), 0, c->stream,
                        (const uint32_t*)codes0, (const uint32_t*)kv0, (const int32_t*)g.gmisc, make_divw(W), epi, keys[0],
                        vals[0], (uint2*)c->hrec.p, g.bs);
@@ -1627,6 +1670,8 @@ int run_hashtable_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_sett
   }
   {
     Timed t(c, KID_GLOBAL_MATCH);
+    c->launch_name[KID_GLOBAL_MATCH][0] = 0;
+    name_join_launch(c, "gpc::k_ht_pairs", false);
     const int nhp = (g.nmax + HP_TILE - 1) / HP_TILE;  // <= nmblk, so the match-block counters are large enough
     hipLaunchKernelGGL((gpc::k_ht_pairs<false>), dim3(nhp, npairs), dim3(HP_THREADS), 0, c->stream,
                        (const uint32_t*)keys[1], (const uint32_t*)vals[1], (const uint2*)c->hrec.p, keys[0],
