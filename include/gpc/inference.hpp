@@ -48,6 +48,7 @@ struct Score;
 }  // namespace evaluation
 namespace tracking {  // gpc/tracking.hpp (extension: point tracks over a frame sequence)
 struct Track;
+class TrackStream;
 }  // namespace tracking
 namespace inference {
 
@@ -476,6 +477,7 @@ class Forest {
   }
 
  private:
+  friend class tracking::TrackStream;  // (gpc/tracking.hpp: hands the forest over as the match calls do)
   evaluation::Score scoreWith(detail::ContextHolder& h, ndb::Buffer<uint8_t>& simg, ndb::Buffer<uint8_t>& timg,
                               InferenceSettings settings, const evaluation::Truth& truth, const std::vector<float>& thresholds);
   // What the reference's caller does next -- preprocessImage x2, rectifiedMatch / matchPair on images of this size --

@@ -6,6 +6,8 @@
 //   Forest::trackSequence(frames, fm, s, n)   sequenceMatch + linking in one call; tracks of at least n records
 //   gpc::tracking::trackRecords(records, ..)  the same for correspondences the caller holds (no forest needed)
 //   gpc::tracking::assemble(records, next, n) the host part alone: Track vectors from records and their links
+//   gpc::tracking::TrackStream                frames pushed as they arrive, track ids kept alive across pushes
+//                                             (gpc_hip_track_stream_*): a video without a known end
 //
 // Errors are reported as everywhere in inference.hpp: an empty result and lastStatus() / lastError().
 #ifndef GPC_AMD_TRACKING_HPP
@@ -105,6 +107,123 @@ inline std::vector<Track> trackRecords(const std::vector<std::vector<ndb::Corres
   }
   return assemble(records, detail::links(next, counts, (int)cap), minLength);
 }
+
+// A video that arrives a frame or a few frames at a time: every push returns the new pairs' correspondences with, per
+// record, the index of its predecessor in the pair before (-1: it starts a track) and its track id -- the ids the offline
+// Forest::trackSequence over all frames so far would give.  The track table stays on the device; tracks() reads rows of it.
+// One stream object per video.  It lives on the context inference.hpp keeps for the CALLING THREAD: create, push and
+// destroy it on one thread, and before that thread ends (another thread's context does not know the stream and cannot
+// release it).  Every push hands the stream's own forest over, as the match calls do; a Forest call with ANOTHER forest on
+// the same thread between two pushes makes the carried codes meaningless, and every later push then fails with
+// GPC_E_INVALID until reset().
+class TrackStream {
+ public:
+  struct Pair {                                  // one new pair of consecutive frames
+    int pair = 0;                                // its global index: frames pair and pair + 1
+    std::vector<ndb::Correspondence> records;
+    std::vector<int32_t> prev, trackId;          // per record
+  };
+  // capPerPair / trackCap <= 0: a quarter of the pixels per pair / four times the pixels in all
+  TrackStream(int width, int height, const inference::Forest::FilterMask& fm, inference::InferenceSettings settings, int capPerPair = 0,
+              int trackCap = 0)
+      : w_(width), h_(height), fm_(fm) {
+    namespace inf = gpc::inference;
+    inf::detail::ContextHolder& h = inf::detail::holder();
+    if (!h.ctx) return;
+    const size_t n = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
+    cap_ = capPerPair > 0 ? capPerPair : (int)std::max<size_t>(1024, n / 4);
+    trackCap_ = trackCap > 0 ? trackCap : (int)std::max<size_t>(4096, 4 * n);
+    const gpc_settings s = settings.toC();
+    const int st = gpc_hip_track_stream_create(h.ctx, width, height, &s, cap_, trackCap_, &s_);
+    if (st != GPC_OK) inf::detail::fail(st, h.ctx, "gpc_hip_track_stream_create");
+  }
+  ~TrackStream() {
+    if (s_) (void)gpc_hip_track_stream_destroy(gpc::inference::detail::holder(true).ctx, s_);
+  }
+  TrackStream(const TrackStream&) = delete;
+  TrackStream& operator=(const TrackStream&) = delete;
+
+  bool valid() const { return s_ != nullptr; }
+  int framesSeen() const { return frames_; }
+  int tracksSoFar() const { return total_; }
+
+  // One frame, or a span of frames in arrival order -> the pairs they complete (none for the very first frame).  A pair
+  // with more than capPerPair records is cut to its first capPerPair (lastStatus() is GPC_E_CAPACITY then).
+  std::vector<Pair> push(ndb::Buffer<uint8_t>& frame) { return push(&frame, 1); }
+  std::vector<Pair> push(std::vector<ndb::Buffer<uint8_t>>& frames) { return push(frames.data(), frames.size()); }
+  std::vector<Pair> push(ndb::Buffer<uint8_t>* frames, size_t count) {
+    namespace inf = gpc::inference;
+    typedef std::vector<Pair> Result;
+    bool ok = s_ != nullptr && count >= 1 && count <= 65535;
+    for (size_t f = 0; ok && f < count; ++f) ok = frames[f].cols() == w_ && frames[f].rows() == h_;
+    if (!ok) {
+      inf::detail::fail(GPC_E_INVALID, nullptr, "gpc_hip_track_stream_push");
+      return Result();
+    }
+    inf::detail::ContextHolder& h = inf::detail::holder();
+    if (!h.ctx || !inf::Forest::upload(h, fm_)) return Result();
+    const size_t n = (size_t)w_ * h_, slots = count * (size_t)cap_;
+    std::vector<uint8_t> fr(n * count);
+    for (size_t f = 0; f < count; ++f) std::memcpy(&fr[n * f], frames[f].data(), n);
+    std::vector<gpc_correspondence> corr(slots);
+    std::vector<int32_t> counts(count), prev(slots, -1), id(slots, -1);
+    int k = 0;
+    int32_t total = 0;
+    const int st = gpc_hip_track_stream_push(h.ctx, s_, fr.data(), (int)count, corr.data(), counts.data(), nullptr, prev.data(),
+                                             id.data(), &k, &total);
+    if (st != GPC_OK) inf::detail::fail(st, h.ctx, "gpc_hip_track_stream_push");
+    if (st != GPC_OK && st != GPC_E_CAPACITY) return Result();
+    Result out((size_t)k);
+    const int pair0 = frames_ > 0 ? frames_ - 1 : 0;
+    for (int t = 0; t < k; ++t) {
+      const int m = std::min(std::max(counts[(size_t)t], 0), cap_);
+      const size_t at = (size_t)t * cap_;
+      out[(size_t)t].pair = pair0 + t;
+      out[(size_t)t].records.reserve((size_t)m);
+      for (int i = 0; i < m; ++i) {
+        const gpc_correspondence& c = corr[at + i];
+        out[(size_t)t].records.push_back(ndb::Correspondence(ndb::Point(c.src_x, c.src_y), ndb::Point(c.tar_x, c.tar_y)));
+      }
+      out[(size_t)t].prev.assign(prev.begin() + at, prev.begin() + at + m);
+      out[(size_t)t].trackId.assign(id.begin() + at, id.begin() + at + m);
+    }
+    frames_ += (int)count;
+    total_ = total;
+    return out;
+  }
+
+  // rows [first, first + n) of the track table that exist (first_pair is a global pair index)
+  std::vector<gpc_track> tracks(int first, int n) {
+    namespace inf = gpc::inference;
+    inf::detail::ContextHolder& h = inf::detail::holder();
+    std::vector<gpc_track> rows((size_t)std::max(n, 0));
+    int32_t total = 0;
+    const int st = (s_ && h.ctx) ? gpc_hip_track_stream_read_tracks(h.ctx, s_, first, n, rows.data(), &total) : GPC_E_INVALID;
+    if (st != GPC_OK) {
+      inf::detail::fail(st, h.ctx, "gpc_hip_track_stream_read_tracks");
+      return std::vector<gpc_track>();
+    }
+    total_ = total;
+    rows.resize((size_t)std::max(0, std::min(first + n, (int)total) - first));
+    return rows;
+  }
+
+  // a new video: frames forgotten, ids restart at 0
+  bool reset() {
+    namespace inf = gpc::inference;
+    inf::detail::ContextHolder& h = inf::detail::holder();
+    const int st = (s_ && h.ctx) ? gpc_hip_track_stream_reset(h.ctx, s_) : GPC_E_INVALID;
+    if (st != GPC_OK) inf::detail::fail(st, h.ctx, "gpc_hip_track_stream_reset");
+    if (st == GPC_OK) frames_ = total_ = 0;
+    return st == GPC_OK;
+  }
+
+ private:
+  int w_ = 0, h_ = 0, cap_ = 0, trackCap_ = 0, frames_ = 0;
+  int32_t total_ = 0;
+  inference::Forest::FilterMask fm_;
+  gpc_hip_track_stream* s_ = nullptr;
+};
 
 }  // namespace tracking
 

@@ -561,10 +561,94 @@ int gpc_hip_track_records(gpc_hip_ctx* ctx, const gpc_correspondence* corr, int 
  *   (nframes - 2) * W * H * 4  +  (nframes - 1) * cap_per_pair * 4              bytes of linking workspace (plus 4 bytes
  *   per 2048 record slots for the head counts), and
  *   what gpc_hip_match_sequence_device keeps for nframes frames (smoothed image, gradient image and codes: 6 bytes per
- *   pixel and frame, plus the chosen matcher's own workspaces).  Longer videos: overlapping calls, stitched by the caller. */
+ *   pixel and frame, plus the chosen matcher's own workspaces).  Longer videos, and videos without a known end: a track
+ *   stream (gpc_hip_track_stream_*, below), which takes the frames in pushes and gives the same ids. */
 int gpc_hip_track_sequence(gpc_hip_ctx* ctx, const uint8_t* frames, int width, int height, int nframes,
                            const gpc_settings* settings, gpc_correspondence* corr, int cap_per_pair, int32_t* counts,
                            int32_t* ncand, int32_t* next, int32_t* track_id, gpc_track* tracks, int track_cap, int32_t* n_tracks);
+
+/* ---- track streams: frames pushed as they arrive, tracks kept alive across calls ------ */
+/* The tracks above for a video that arrives one frame or a few frames at a time and has no known end.  A stream belongs
+ * to a context and carries what linking the next pair needs; nothing in it grows with the length of the video except the
+ * track table, whose size is fixed at creation.  The linking rule makes this exact: whether record (t, i) is a head
+ * depends on pairs t - 1 and t alone, and heads are numbered by (t ascending, i ascending), so ids can be handed out as
+ * pairs arrive.  AFTER ANY SEQUENCE OF PUSHES, EVERYTHING DELIVERED SO FAR IS BYTE-IDENTICAL TO WHAT THE OFFLINE CALL
+ * (gpc_hip_track_sequence_device, gpc_hip_track_records_device) OVER THE CONCATENATED FRAMES OR RECORDS RETURNS.
+ *
+ * Pair numbering: pairs are numbered globally since create or reset; pair g joins frames g and g + 1.
+ * A push that produces k pairs fills slots 0 .. k-1 of its outputs, each [k][cap_per_pair] like the offline arrays:
+ *   corr, counts   as gpc_hip_match_sequence_device documents them;
+ *   ncand          (optional) [nframes]: the candidates of each frame OF THIS PUSH, so that the pushes' arrays laid end to
+ *                  end are the offline ncand;
+ *   track_id[p][i] the offline track_id of that record;
+ *   prev[p][i]     the index, in the preceding global pair, of the record whose offline `next` equals i, or -1.  prev
+ *                  replaces next because a pair's next is not known until the following push; prev is its exact inverse
+ *                  and is known at once.  For global pair 0 every prev is -1.
+ *   Entries at i >= m_t are left untouched.
+ * Track table: gpc_track rows with first_pair as a GLOBAL pair index, track_cap of them, in the stream.  New heads write
+ *   their row; a continued track has length and last_record updated by the one record that continues it.  Rows with
+ *   id >= track_cap are neither written nor updated; ids are still assigned.  The running total is a device word.  After
+ *   every push the table and the total equal the offline result over the pairs pushed so far.
+ * Id bound: track ids are 31 bits.  The stream keeps a host-side upper bound on the total, += k * min(cap_per_pair,
+ *   width * height) per push; a push that could pass 2^31 - 1 returns GPC_E_UNSUPPORTED and changes nothing.  The calls
+ *   that read the true total back (the host push, _state, _read_tracks) tighten the bound to it.  The limits of the offline
+ *   form apply to ONE push: k <= 65535 (65534 once a pair is carried: the window holds it too) and k * cap_per_pair <=
+ *   2^31 - 1.
+ *
+ * A push yields nframes pairs once a frame has been seen, else nframes - 1; a first push of one frame yields 0 pairs and
+ * is valid.  Waiting is as for gpc_hip_match_sequence_device: the epipolar sort matcher only queues on the context's
+ * stream, the device-wide matchers wait once on the host inside the call.  A stream is fed EITHER frames OR records
+ * between resets: mixing them is GPC_E_INVALID.  Refusals (the stream is left as it was): group mode GPC_E_UNSUPPORTED;
+ * no forest (frames) GPC_E_NO_FOREST; nframes < 1, null pointers, no settings at creation (frames), a destroyed stream or
+ * a stream of another context GPC_E_INVALID; a forest or arithmetic of the context that CHANGED since the stream's last
+ * push of frames (gpc_hip_set_forest* with other tests, gpc_hip_set_arithmetic with another mode: the carried codes are
+ * then meaningless) GPC_E_INVALID until _reset.  A pair with more than cap_per_pair records: the stream advances, the
+ * first cap_per_pair records are the ones linked, as offline, and the host push returns GPC_E_CAPACITY.
+ * The stream owns everything it carries: any other call on the context between two pushes (batches of another size,
+ * sequences, offline tracks, consensus, another stream) leaves what it returns unchanged.  With two lanes the lanes are
+ * drained, as for sequences.
+ *
+ * Device memory of a stream (cap = cap_per_pair):
+ *   cap * 20  +  max(track_cap, 1) * 16  +  16               bytes from creation (the carried pair's records and ids, the
+ *                                                            table, the carried count and the total), and
+ *   width * height * 4  +  16                                bytes from the first push of frames (the last frame's code
+ *                                                            image and statistics words; smoothed and gradient images are
+ *                                                            not carried), plus width * height under Naive arithmetic
+ *                                                            with a 32-test forest (the candidate bytes the joins read);
+ *   (k + 1) * cap * 4                                        bytes of link workspace of the largest push so far.
+ * The context's own workspaces serve a push as they serve the offline calls: 4 * width * height + 4 * cap bytes per pair of
+ * the push (planes and predecessors), 4 bytes per 2048 record slots, and what gpc_hip_match_sequence_device keeps for
+ * nframes + 1 frames. */
+typedef struct gpc_hip_track_stream gpc_hip_track_stream;
+/* settings: copied; NULL for a stream that will only be given records.  width, height: the frames' (the records form
+ * takes any positive size, as gpc_hip_track_records_device does; the frames form needs what the matchers need). */
+int gpc_hip_track_stream_create(gpc_hip_ctx* ctx, int width, int height, const gpc_settings* settings, int cap_per_pair,
+                                int track_cap, gpc_hip_track_stream** out);
+/* Waits for the context's stream.  gpc_hip_destroy destroys the streams that are left. */
+int gpc_hip_track_stream_destroy(gpc_hip_ctx* ctx, gpc_hip_track_stream* s);
+/* A new video: frames forgotten, ids restart at 0, the table's rows count as unwritten. */
+int gpc_hip_track_stream_reset(gpc_hip_ctx* ctx, gpc_hip_track_stream* s);
+/* nframes frames in HBM.  *npairs = k, known when the call returns; the arrays after a wait on the context's stream. */
+int gpc_hip_track_stream_push_device(gpc_hip_ctx* ctx, gpc_hip_track_stream* s, const uint8_t* d_frames, int nframes,
+                                     gpc_correspondence* d_corr, int32_t* d_counts, int32_t* d_ncand, int32_t* d_prev,
+                                     int32_t* d_track_id, int* npairs);
+/* The same from / to host memory (pageable or page-locked), synchronous; *n_tracks is the total so far.  GPC_E_CAPACITY
+ * when a pair's count exceeds cap_per_pair (a table that is too small shows in *n_tracks > track_cap). */
+int gpc_hip_track_stream_push(gpc_hip_ctx* ctx, gpc_hip_track_stream* s, const uint8_t* frames, int nframes,
+                              gpc_correspondence* corr, int32_t* counts, int32_t* ncand, int32_t* prev, int32_t* track_id,
+                              int* npairs, int32_t* n_tracks);
+/* npairs >= 1 pairs of records on the device in the layout gpc_hip_match_sequence_device writes.  No forest is needed;
+ * the call only queues work on the context's stream. */
+int gpc_hip_track_stream_push_records_device(gpc_hip_ctx* ctx, gpc_hip_track_stream* s, const gpc_correspondence* d_corr,
+                                             const int32_t* d_counts, int npairs, int32_t* d_prev, int32_t* d_track_id);
+/* Waits for the context's stream.  Every output is optional. */
+int gpc_hip_track_stream_state(gpc_hip_ctx* ctx, gpc_hip_track_stream* s, int* frames_seen, int* pairs_seen, int32_t* n_tracks);
+/* The table and the total as device pointers, valid until _destroy; read them behind the context's stream. */
+int gpc_hip_track_stream_table(gpc_hip_track_stream* s, const gpc_track** d_tracks, const int32_t** d_ntracks);
+/* Rows [first, first + n) to host memory, synchronous; rows at *n_tracks and beyond do not exist yet and are not written.
+ * first + n > track_cap: GPC_E_CAPACITY (*n_tracks is still delivered). */
+int gpc_hip_track_stream_read_tracks(gpc_hip_ctx* ctx, gpc_hip_track_stream* s, int first, int n, gpc_track* out,
+                                     int32_t* n_tracks);
 
 /* ---- match filtering: grid motion consensus ---------------------------------------- */
 /* Rejects the matches their neighbours do not agree with: grid-based motion statistics (GMS, Bian et al., CVPR 2017) -- a

@@ -111,6 +111,9 @@ SYMBOLS = [
     "gpc_hip_track_records_device", "gpc_hip_track_sequence_device", "gpc_hip_track_records", "gpc_hip_track_sequence",
     "gpc_hip_consensus_supports_device", "gpc_hip_consensus_correspondences_device", "gpc_hip_consensus_batch_device",
     "gpc_hip_consensus_sequence_device", "gpc_hip_consensus_supports", "gpc_hip_consensus_correspondences",
+    "gpc_hip_track_stream_create", "gpc_hip_track_stream_destroy", "gpc_hip_track_stream_reset",
+    "gpc_hip_track_stream_push_device", "gpc_hip_track_stream_push", "gpc_hip_track_stream_push_records_device",
+    "gpc_hip_track_stream_state", "gpc_hip_track_stream_table", "gpc_hip_track_stream_read_tracks",
 ]
 
 
@@ -190,6 +193,19 @@ def load():
                                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_void_p]
     L.gpc_hip_track_sequence.argtypes = L.gpc_hip_track_sequence_device.argtypes
+    L.gpc_hip_track_stream_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Settings), C.c_int, C.c_int,
+                                              C.POINTER(C.c_void_p)]
+    L.gpc_hip_track_stream_destroy.argtypes = [C.c_void_p, C.c_void_p]
+    L.gpc_hip_track_stream_reset.argtypes = [C.c_void_p, C.c_void_p]
+    L.gpc_hip_track_stream_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    L.gpc_hip_track_stream_push.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int32)]
+    L.gpc_hip_track_stream_push_records_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                           C.c_void_p]
+    L.gpc_hip_track_stream_state.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int32)]
+    L.gpc_hip_track_stream_table.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.gpc_hip_track_stream_read_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
     L.gpc_hip_consensus_supports_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(Consensus), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.gpc_hip_consensus_correspondences_device.argtypes = L.gpc_hip_consensus_supports_device.argtypes
@@ -830,6 +846,11 @@ class Context:
         self._ck(st, allow=(E_CAPACITY,))
         return out, counts, ncand, nxt, tid, rows[:min(n.value, track_cap)], n.value, st
 
+    def track_stream(self, width, height, settings, cap_per_pair, track_cap):
+        """A TrackStream of this context (gpc_hip_track_stream_create): frames or records pushed as they arrive, track ids
+        kept across pushes.  settings None: a stream that is only given records."""
+        return TrackStream(self, width, height, settings, cap_per_pair, track_cap)
+
     # ---- match filtering (gpc_hip_consensus_*): grid motion consensus over a pair's records
     def consensus_records_device(self, d_rec, corr, cap_per_pair, d_counts, width, height, npairs, prm, d_keep, d_out, cap_out,
                                  d_index, d_out_counts):
@@ -961,6 +982,89 @@ class Context:
             self._ck(self.L.gpc_hip_kernel_time(self.h, i, C.byref(ms), C.byref(n)))
             out[self.L.gpc_hip_kernel_name(i).decode()] = (ms.value, n.value)
         return out
+
+
+class TrackStream:
+    """One gpc_hip_track_stream of a Context: what the offline track calls return for the frames (or records) pushed so
+    far, delivered push by push.  The device forms take raw device pointers and only queue work (the device-wide matchers
+    wait once inside the call); push() takes host frames and is synchronous."""
+
+    def __init__(self, ctx, width, height, settings, cap_per_pair, track_cap):
+        self.ctx = ctx
+        self.h = None
+        self.width, self.height, self.cap, self.track_cap = int(width), int(height), int(cap_per_pair), int(track_cap)
+        h = C.c_void_p()
+        ctx._ck(ctx.L.gpc_hip_track_stream_create(ctx.h, self.width, self.height, C.byref(settings) if settings is not None else None,
+                                                  self.cap, self.track_cap, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.L.gpc_hip_track_stream_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    def reset(self):
+        self.ctx._ck(self.ctx.L.gpc_hip_track_stream_reset(self.ctx.h, self.h))
+
+    def push_device(self, d_frames, nframes, d_corr, d_counts, d_ncand, d_prev, d_track_id):
+        """nframes frames in HBM -> the number of pairs produced; outputs [k][cap] (d_ncand [nframes], optional)"""
+        k = C.c_int()
+        self.ctx._ck(self.ctx.L.gpc_hip_track_stream_push_device(self.ctx.h, self.h, C.c_void_p(d_frames), int(nframes),
+                                                                 C.c_void_p(d_corr), C.c_void_p(d_counts), C.c_void_p(d_ncand or 0),
+                                                                 C.c_void_p(d_prev), C.c_void_p(d_track_id), C.byref(k)))
+        return k.value
+
+    def push_records_device(self, d_corr, d_counts, npairs, d_prev, d_track_id):
+        self.ctx._ck(self.ctx.L.gpc_hip_track_stream_push_records_device(self.ctx.h, self.h, C.c_void_p(d_corr), C.c_void_p(d_counts),
+                                                                         int(npairs), C.c_void_p(d_prev), C.c_void_p(d_track_id)))
+
+    def push(self, frames, fill=-1, alloc=None):
+        """Host frames [n, H, W] (or one frame [H, W]) -> (records [k, cap] of CORR_DTYPE, counts [k], ncand [n], prev [k, cap],
+        track_id [k, cap], n_tracks so far, status); entries of prev / track_id beyond a pair's count hold `fill`.
+        alloc(shape, dtype): where the outputs are made (np.empty; Context.pinned_empty for page-locked ones)."""
+        frames = np.asarray(frames)
+        if frames.ndim == 2:
+            frames = frames[None]
+        frames = _host_frames(frames)
+        n, H, W = frames.shape
+        if (W, H) != (self.width, self.height):
+            raise ValueError("frames must be %d x %d" % (self.width, self.height))
+        alloc = alloc or np.empty
+        rows = max(n, 1)
+        out = alloc((rows, self.cap), CORR_DTYPE)
+        counts = alloc((rows,), np.int32)
+        ncand = alloc((rows,), np.int32)
+        prev = alloc((rows, self.cap), np.int32)
+        tid = alloc((rows, self.cap), np.int32)
+        prev[...] = fill
+        tid[...] = fill
+        k, total = C.c_int(), C.c_int32()
+        st = self.ctx.L.gpc_hip_track_stream_push(self.ctx.h, self.h, _ptr(frames), n, _ptr(out), _ptr(counts), _ptr(ncand),
+                                                  _ptr(prev), _ptr(tid), C.byref(k), C.byref(total))
+        self.ctx._ck(st, allow=(E_CAPACITY,))
+        k = k.value
+        return out[:k], counts[:k], ncand[:n], prev[:k], tid[:k], total.value, st
+
+    def state(self):
+        """(frames seen, pairs seen, tracks so far); waits for the context's stream"""
+        f, p, n = C.c_int(), C.c_int(), C.c_int32()
+        self.ctx._ck(self.ctx.L.gpc_hip_track_stream_state(self.ctx.h, self.h, C.byref(f), C.byref(p), C.byref(n)))
+        return f.value, p.value, n.value
+
+    def table(self):
+        """(device pointer of the table [track_cap] of TRACK_DTYPE, device pointer of the int32 total)"""
+        t, n = C.c_void_p(), C.c_void_p()
+        self.ctx._ck(self.ctx.L.gpc_hip_track_stream_table(self.h, C.byref(t), C.byref(n)))
+        return t.value, n.value
+
+    def read_tracks(self, first=0, n=None, fill=-1):
+        """(rows [first, first + n) that exist as a TRACK_DTYPE array, tracks so far); n None: up to the table's end"""
+        n = self.track_cap - first if n is None else int(n)
+        rows = np.full((max(n, 1), 4), fill, np.int32)
+        total = C.c_int32()
+        self.ctx._ck(self.ctx.L.gpc_hip_track_stream_read_tracks(self.ctx.h, self.h, int(first), n, _ptr(rows), C.byref(total)))
+        have = max(0, min(first + n, total.value) - first)
+        return rows[:have].view(TRACK_DTYPE).reshape(-1), total.value
 
 
 class TrainSet:

@@ -39,8 +39,10 @@
 #include "k_rows.h"
 #include "k_score.h"
 #include "k_track.h"
+#include "k_track_stream.h"
 #include "k_train.h"
 #include "k_union.h"
+#include "track_stream_host.h"
 
 namespace {
 
@@ -67,6 +69,14 @@ enum KernelId {
   KID_CONS_COUNT,
   KID_CONS_BLOCKS,
   KID_CONS_WRITE,
+  KID_TRS_FILL,
+  KID_TRS_SCATTER,
+  KID_TRS_LINK,
+  KID_TRS_SETTLE,
+  KID_TRS_SCAN,
+  KID_TRS_WALK,
+  KID_TRS_SAVE,
+  KID_TRS_NCAND,
   KID_SCORE_RECORDS,
   KID_SCORE_MATCHABLE,
   KID_COUNT
@@ -76,6 +86,7 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_mask", "k_global_keys", "k_global_sort", "k_global_match", "k_train_eval", "k_group_union",
     "k_track_fill", "k_track_scatter", "k_track_link", "k_track_settle", "k_track_scan", "k_track_walk",
     "k_cons_cells", "k_cons_scan", "k_cons_scatter", "k_cons_count", "k_cons_blocks", "k_cons_write",
+    "k_trs_fill", "k_trs_scatter", "k_trs_link", "k_trs_settle", "k_trs_scan", "k_trs_walk", "k_trs_save", "k_trs_ncand",
     "k_score_records", "k_score_matchable"};
 
 struct DevBuf {
@@ -314,6 +325,8 @@ struct gpc_hip_ctx {
   std::vector<TimedSpan> free_spans;
 
   std::vector<gpc_hip_train_set*> train_sets;  // training sets created on this context
+  std::vector<gpc_hip_track_stream*> track_streams;  // track streams created on this context
+  uint64_t code_gen = 1;  // counts the changes of forest and arithmetic: codes hashed under another value are not comparable
   // gpc_hip_extract_triplets: raw (host entry only), smooth and grad of one chunk of frame pairs, the chunk's column groups
   // (allocated by the call, released before it returns)
   DevBuf ext_raw, ext_smooth, ext_grad, ext_groups;
@@ -701,7 +714,7 @@ int run_hashtable_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_sett
 // d_smooth_out / d_grad_out: where the images go instead of the context's workspaces (byte gradient image only)
 int run_preprocess(gpc_hip_ctx* c, const uint8_t* d_raw0, const uint8_t* d_raw1, int W, int H,
                    int npairs, int sides, int thr, bool gradbits = false, uint8_t* d_smooth_out = nullptr,
-                   uint8_t* d_grad_out = nullptr) {
+                   uint8_t* d_grad_out = nullptr, int32_t* d_stats = nullptr) {
   const int nimg = npairs * sides;
   const size_t n = (size_t)W * H;
   if (!d_smooth_out) {
@@ -712,7 +725,12 @@ int run_preprocess(gpc_hip_ctx* c, const uint8_t* d_raw0, const uint8_t* d_raw1,
   } else {
     gradbits = false;
   }
-  CHK(ensure(c, c->stats, sizeof(int32_t) * GPC_STAT_STRIDE * nimg));
+  // d_stats: where the images' statistics words go instead of the head of c->stats (a track stream keeps slot 0 for the
+  // carried frame)
+  if (!d_stats) {
+    CHK(ensure(c, c->stats, sizeof(int32_t) * GPC_STAT_STRIDE * nimg));
+    d_stats = (int32_t*)c->stats.p;
+  }
   // threshold^2 passes through _mm_set1_epi16 in the SSE build (filter.hpp:418); sobelNaive keeps the int (:159)
   const int thr_sq = c->naive ? (thr & 0xFF) * (thr & 0xFF) : (int)(int16_t)(uint16_t)((thr & 0xFF) * (thr & 0xFF));
   // Rows per thread (the strip a thread marches down): 14 read every raw row 1.14 times and are what a launch that fills the
@@ -740,7 +758,7 @@ int run_preprocess(gpc_hip_ctx* c, const uint8_t* d_raw0, const uint8_t* d_raw1,
            c->grad_is_bits ? ", true" : "");
 #define LAUNCH_PRE(NAIVE, ROWS, BITS)                                                                        \
   hipLaunchKernelGGL((gpc::k_preprocess<NAIVE, ROWS, BITS>), grid, dim3(PP_TX * PP_TY), 0, c->stream, d_raw0, d_raw1, \
-                     d_smooth_out, d_grad_out, W, H, sides, thr_sq, (int32_t*)c->stats.p)
+                     d_smooth_out, d_grad_out, W, H, sides, thr_sq, d_stats)
 #define LAUNCH_PRE_ROWS(NAIVE, BITS)                                  \
   do {                                                                \
     if (rows == PP_ROWS) LAUNCH_PRE(NAIVE, PP_ROWS, BITS);            \
@@ -763,7 +781,7 @@ int run_preprocess(gpc_hip_ctx* c, const uint8_t* d_raw0, const uint8_t* d_raw1,
 // groups > 0: k_hash_groups over the context's groups (gpc_hip_set_forest_groups), image 2p + s writing group g as image
 // (p * groups + g) * 2 + s (gstep 2) or, one image, g (gstep 1); the statistics of those virtual images in c->stats
 int run_hash(gpc_hip_ctx* c, const uint8_t* d_smooth, const uint8_t* d_grad, const uint8_t* d_cand,
-             int W, int H, int nimg, bool dense, uint32_t* d_codes, int groups = 0, int gstep = 2) {
+             int W, int H, int nimg, bool dense, uint32_t* d_codes, int groups = 0, int gstep = 2, int32_t* d_stats = nullptr) {
   if (!c->have_forest) return GPC_E_NO_FOREST;
   // tiles per workgroup: each CU holds 2 workgroups (67 KiB of LDS each); walking several
   // vertically adjacent tiles hides the next window's load latency, but the grid must still fill
@@ -823,7 +841,7 @@ int run_hash(gpc_hip_ctx* c, const uint8_t* d_smooth, const uint8_t* d_grad, con
   const int last_from = nwg_all > slots ? (int)(nwg_all - slots) : 0;
   Timed t(c, KID_HASH);
   const bool tau = groups > 0 ? c->gtau : c->forest.type != 0;
-  int32_t* st = (int32_t*)c->stats.p;
+  int32_t* st = d_stats ? d_stats : (int32_t*)c->stats.p;  // (d_stats: as for run_preprocess)
   if (groups > 0) {
     const GpcForestDev* gf = (const GpcForestDev*)c->gforest_dev.p;
     snprintf(c->launch_name[KID_HASH], sizeof c->launch_name[0], "gpc::k_hash_groups<%s, %s, %s, %s, %d>", tau ? "true" : "false",
@@ -2210,6 +2228,7 @@ int gpc_hip_destroy(gpc_hip_ctx* c) {
                     &c->sstats, &c->all_rec, &c->all_cnt, &c->stage, &c->tr_plane, &c->tr_pred, &c->tr_blk,
                     &c->cs_key, &c->cs_idx, &c->cs_cur, &c->cs_start, &c->cs_blk, &c->cs_keep};
   while (!c->train_sets.empty()) (void)gpc_hip_train_set_destroy(c, c->train_sets.back());
+  while (!c->track_streams.empty()) (void)gpc_hip_track_stream_destroy(c, c->track_streams.back());
   for (DevBuf* b : bufs) release(*b);
   for (auto& s : c->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
   for (auto& s : c->free_spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -2299,6 +2318,7 @@ int gpc_hip_reserve(gpc_hip_ctx* c, int W, int H, int max_pairs) {
 
 int gpc_hip_set_arithmetic(gpc_hip_ctx* c, int mode) {
   if (!c || (mode != GPC_ARITH_SSE && mode != GPC_ARITH_NAIVE)) return GPC_E_INVALID;
+  if (c->naive != (mode == GPC_ARITH_NAIVE)) ++c->code_gen;
   c->naive = (mode == GPC_ARITH_NAIVE);
   return GPC_OK;
 }
@@ -2438,6 +2458,7 @@ int gpc_hip_set_forest(gpc_hip_ctx* c, const gpc_filter_mask* fm) {
     return GPC_OK;
   GpcForestDev f, fn, ft;
   CHK(forest_dev_of(fm, f, fn, ft));
+  ++c->code_gen;
   c->forest = f;
   c->forest_naive = fn;
   HIPCHK(c, hipSetDevice(c->device));
@@ -2545,6 +2566,7 @@ int gpc_hip_set_forest_groups(gpc_hip_ctx* c, const gpc_filter_mask* groups, int
     tau = tau || fm->type != 0;
   }
   HIPCHK(c, hipSetDevice(c->device));
+  ++c->code_gen;
   CHK(ensure(c, c->gforest_dev, sizeof(GpcForestDev) * dev.size()));
   CHK(drain_lanes(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // a launch in flight may still read the previous tests
@@ -3849,6 +3871,332 @@ int gpc_hip_track_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, 
                                     (int32_t*)st.p(r.nc), (int32_t*)st.p(r.next), (int32_t*)st.p(r.id), (gpc_track*)st.p(r.tab),
                                     track_cap, (int32_t*)st.p(r.nt)));
   return track_down(st, r, npairs, cap, track_cap, corr, counts, ncand, next, track_id, tracks, ntracks);
+}
+
+// ------------------------------------------------------------------ track streams: tracks kept alive across pushes
+
+// What a stream carries from one push to the next, all of it the stream's own device memory (include/gpc_hip.h has the
+// byte formula): the last frame's code image, statistics words and (WIDE joins) candidate bytes; the last pair's records,
+// count and track ids; the track table and the running total.  The window's `next` is workspace of the stream; planes,
+// predecessors and head counts are the context's (tr_plane, tr_pred, tr_blk), as for the offline calls.
+struct gpc_hip_track_stream {
+  gpc::TrsBook book;
+  gpc_settings settings;
+  bool have_settings = false;
+  uint32_t* codes = nullptr;      // [H][W], allocated by the first push of frames
+  uint8_t* cand = nullptr;        // [H][W], allocated by the first push of frames under 32-bit Naive codes
+  int32_t* fstats = nullptr;      // GPC_STAT_STRIDE words
+  gpc::TrRec* crec = nullptr;     // [cap]
+  int32_t* cid = nullptr;         // [cap]
+  int32_t* words = nullptr;       // [0] the carried pair's count (clamped), [1] the number of tracks
+  gpc_track* table = nullptr;     // [max(track_cap, 1)]
+  DevBuf nextw;                   // [c + k][cap] of the largest push so far
+};
+
+namespace {
+
+int trs_check(gpc_hip_ctx* c, gpc_hip_track_stream* s) {
+  if (!c || !s) return GPC_E_INVALID;
+  for (gpc_hip_track_stream* t : c->track_streams)   // (a destroyed stream, or another context's, is not in the list)
+    if (t == s) return GPC_OK;
+  return GPC_E_INVALID;
+}
+
+void trs_free(gpc_hip_track_stream* s) {
+  void* mem[] = {s->codes, s->cand, s->fstats, s->crec, s->cid, s->words, s->table};
+  for (void* p : mem)
+    if (p) (void)hipFree(p);
+  release(s->nextw);
+  delete s;
+}
+
+// The link steps over the window [carried pair, k new pairs] whose new records are on the device, then the carry of the
+// next push.  Only queues work on the context's stream.
+int trs_link(gpc_hip_ctx* c, gpc_hip_track_stream* s, const gpc_correspondence* d_corr, const int32_t* d_counts,
+             const gpc::TrsPush& p, int32_t* d_prev, int32_t* d_track_id) {
+  const int W = s->book.W, H = s->book.H, cap = s->book.cap, k = p.k, cy = p.carry;
+  const size_t n = (size_t)W * H;
+  const long nchunk = ((long)cap + TR_CHUNK - 1) / TR_CHUNK;
+  const long n16 = (long)((n * (size_t)k + 3) / 4);  // (the last group may reach into the slack ensure() leaves)
+  CHK(ensure(c, c->tr_plane, sizeof(int32_t) * n * (size_t)k));
+  CHK(ensure(c, c->tr_pred, sizeof(int32_t) * (size_t)cap * k));
+  CHK(ensure(c, c->tr_blk, sizeof(int32_t) * (size_t)nchunk * k));
+  CHK(ensure(c, s->nextw, sizeof(int32_t) * (size_t)cap * (size_t)(cy + k)));
+  const gpc::TrRec* rec = (const gpc::TrRec*)d_corr;
+  int32_t* plane = (int32_t*)c->tr_plane.p;
+  int32_t* pred = (int32_t*)c->tr_pred.p;
+  int32_t* blk = (int32_t*)c->tr_blk.p;
+  int32_t* next = (int32_t*)s->nextw.p;
+  const int32_t* cm = s->words;
+  int32_t* total = s->words + 1;
+  const unsigned gx = (unsigned)(nchunk < 1024 ? nchunk : 1024);
+  const dim3 sgrid(gx, k), wgrid(gx, cy + k), cgrid((unsigned)nchunk, cy + k);
+  {
+    const long fb = (n16 + TR_THREADS - 1) / TR_THREADS;
+    Timed t(c, KID_TRS_FILL);
+    hipLaunchKernelGGL(gpc::k_trs_fill, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(TR_THREADS), 0, c->stream, (int4*)plane, n16);
+  }
+  {
+    Timed t(c, KID_TRS_SCATTER);
+    hipLaunchKernelGGL(gpc::k_trs_scatter, sgrid, dim3(TR_THREADS), 0, c->stream, rec, cap, d_counts, W, H, plane, pred);
+  }
+  {
+    Timed t(c, KID_TRS_LINK);
+    hipLaunchKernelGGL(gpc::k_trs_link, wgrid, dim3(TR_THREADS), 0, c->stream, (const gpc::TrRec*)s->crec, cm, cy, rec, cap, d_counts,
+                       W, H, k, (const int32_t*)plane, pred, next);
+  }
+  {
+    Timed t(c, KID_TRS_SETTLE);
+    hipLaunchKernelGGL(gpc::k_trs_settle, cgrid, dim3(TR_THREADS), 0, c->stream, cm, cy, cap, d_counts, k, (const int32_t*)pred, next,
+                       blk, (int)nchunk);
+  }
+  {
+    Timed t(c, KID_TRS_SCAN);
+    hipLaunchKernelGGL(gpc::k_trs_scan, dim3(1), dim3(1024), 0, c->stream, blk, nchunk * k, total);
+  }
+  {
+    Timed t(c, KID_TRS_WALK);
+    hipLaunchKernelGGL(gpc::k_trs_walk, cgrid, dim3(TR_THREADS), 0, c->stream, cm, (const int32_t*)s->cid, cy, cap, d_counts, k,
+                       (const int32_t*)pred, (const int32_t*)next, (const int32_t*)blk, (int)nchunk, s->book.pairs_seen, d_track_id,
+                       d_prev, (gpc::TrRow*)s->table, s->book.track_cap);
+  }
+  {
+    Timed t(c, KID_TRS_SAVE);
+    hipLaunchKernelGGL(gpc::k_trs_save, dim3(gx), dim3(TR_THREADS), 0, c->stream, rec + (size_t)(k - 1) * cap,
+                       (const int32_t*)d_track_id + (size_t)(k - 1) * cap, d_counts + (k - 1), cap, s->crec, s->cid, s->words);
+  }
+  for (int q = KID_TRS_FILL; q <= KID_TRS_SAVE; ++q) snprintf(c->launch_name[q], sizeof c->launch_name[0], "gpc::%s", kKernelNames[q]);
+  HIPCHK(c, hipGetLastError());
+  return GPC_OK;
+}
+
+int trs_alloc(gpc_hip_ctx* c, void** p, size_t bytes) {
+  if (*p) return GPC_OK;
+  HIPCHK(c, hipMalloc(p, bytes));
+  return GPC_OK;
+}
+
+// every refusal of a push of frames that leaves the stream as it is; on GPC_OK *p says what the push produces
+int trs_frames_usable(gpc_hip_ctx* c, gpc_hip_track_stream* s, int nframes, gpc::TrsPush* p) {
+  CHK(trs_check(c, s));
+  if (!s->have_settings) return GPC_E_INVALID;
+  CHK(match_usable(c, &s->settings, s->book.W, s->book.H, true));
+  return gpc::trs_plan(s->book, gpc::TRS_FRAMES, nframes, c->code_gen, p);
+}
+
+// gpc_hip_match_sequence_device with frame 0 of the layout supplied by the carry instead of computed: the new frames are
+// images off .. off + nframes - 1 of the codes [nimg][H][W] and of the statistics, k_preprocess and k_hash run over them
+// alone and write their statistics words behind slot 0.  Where the joins read candidate bytes (wide_codes) the gradient
+// image takes the same layout; otherwise it is the context's as for any sequence (the bit image where that is taken).
+int trs_push_frames(gpc_hip_ctx* c, gpc_hip_track_stream* s, const uint8_t* d_frames, int nframes, gpc_correspondence* d_corr,
+                    int32_t* d_counts, int32_t* d_ncand, int32_t* d_prev, int32_t* d_track_id, const gpc::TrsPush& p) {
+  const int W = s->book.W, H = s->book.H, cap = s->book.cap;
+  const size_t n = (size_t)W * H;
+  const int off = s->book.frames_seen > 0 ? 1 : 0, nimg = nframes + off, npairs = nimg - 1;
+  const bool wide = wide_codes(c);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->pipeline > 1) CHK(drain_lanes(c));  // (streams run on the context itself, as sequences do)
+  CHK(trs_alloc(c, (void**)&s->codes, sizeof(uint32_t) * n));
+  CHK(trs_alloc(c, (void**)&s->fstats, sizeof(int32_t) * GPC_STAT_STRIDE));
+  if (wide) CHK(trs_alloc(c, (void**)&s->cand, n));
+  CHK(ensure(c, c->codes, sizeof(uint32_t) * n * nimg));
+  CHK(ensure(c, c->stats, sizeof(int32_t) * GPC_STAT_STRIDE * nimg));
+  if (npairs > 0) CHK(ensure(c, c->sstats, sizeof(int32_t) * GPC_STAT_STRIDE * 2 * npairs));
+  uint32_t* codes = (uint32_t*)c->codes.p;
+  int32_t* stats = (int32_t*)c->stats.p;
+  const int thr = s->settings.gradient_threshold;
+  if (wide) {
+    CHK(ensure(c, c->smooth, n * nimg));
+    CHK(ensure(c, c->grad, n * nimg));
+    uint8_t* sm = (uint8_t*)c->smooth.p + n * off;
+    uint8_t* gr = (uint8_t*)c->grad.p + n * off;
+    CHK(run_preprocess(c, d_frames, nullptr, W, H, nframes, 1, thr, false, sm, gr, stats + GPC_STAT_STRIDE * off));
+    CHK(run_hash(c, sm, gr, nullptr, W, H, nframes, false, codes + n * off, 0, 2, stats + GPC_STAT_STRIDE * off));
+    if (off) CHK(dev_copy16(c, c->grad.p, s->cand, n));
+  } else {
+    CHK(run_preprocess(c, d_frames, nullptr, W, H, nframes, 1, thr, true, nullptr, nullptr, stats + GPC_STAT_STRIDE * off));
+    CHK(run_hash(c, (const uint8_t*)c->smooth.p, (const uint8_t*)c->grad.p, nullptr, W, H, nframes, false, codes + n * off, 0, 2,
+                 stats + GPC_STAT_STRIDE * off));
+  }
+  if (off) {
+    CHK(dev_copy16(c, codes, s->codes, sizeof(uint32_t) * n));
+    CHK(dev_copy16(c, stats, s->fstats, sizeof(int32_t) * GPC_STAT_STRIDE));
+  }
+  if (d_ncand) {
+    Timed t(c, KID_TRS_NCAND);
+    snprintf(c->launch_name[KID_TRS_NCAND], sizeof c->launch_name[0], "gpc::k_trs_ncand");
+    hipLaunchKernelGGL(gpc::k_trs_ncand, dim3((nframes + 255) / 256), dim3(256), 0, c->stream,
+                       (const int32_t*)(stats + GPC_STAT_STRIDE * off), d_ncand, nframes);
+    HIPCHK(c, hipGetLastError());
+  }
+  int st = GPC_OK;
+  if (npairs > 0) {
+    const int nthr = 2 * npairs * GPC_STAT_STRIDE;
+    hipLaunchKernelGGL(gpc::k_seq_stats, dim3((nthr + 255) / 256), dim3(256), 0, c->stream, (const int32_t*)stats,
+                       (int32_t*)c->sstats.p, (int32_t*)nullptr, nimg);
+    HIPCHK(c, hipGetLastError());
+    std::swap(c->stats, c->sstats);
+    st = run_match(c, W, H, npairs, &s->settings, 1, (const uint8_t*)c->grad.p, d_corr, cap, d_counts, nullptr, nullptr, true);
+    std::swap(c->stats, c->sstats);
+    if (st != GPC_OK && st != GPC_E_CAPACITY) return st;
+  }
+  // the links first (their workspaces may still fail to grow, and nothing of the carry has been touched by then), then the
+  // carry of the next push: the last frame's codes, statistics and (wide) candidate bytes
+  if (npairs > 0) CHK(trs_link(c, s, d_corr, d_counts, p, d_prev, d_track_id));
+  CHK(dev_copy16(c, s->codes, codes + n * (size_t)(nimg - 1), sizeof(uint32_t) * n));
+  CHK(dev_copy16(c, s->fstats, stats + GPC_STAT_STRIDE * (nimg - 1), sizeof(int32_t) * GPC_STAT_STRIDE));
+  if (wide) CHK(dev_copy16(c, s->cand, (const uint8_t*)c->grad.p + n * (size_t)(nimg - 1), n));
+  gpc::trs_commit(s->book, gpc::TRS_FRAMES, nframes, c->code_gen, p);
+  return st;
+}
+
+// the running total, read back (the stream is waited for); tightens the bound on the ids
+int trs_total(gpc_hip_ctx* c, gpc_hip_track_stream* s, int32_t* total) {
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(total, s->words + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
+  gpc::trs_tighten(s->book, *total);
+  return GPC_OK;
+}
+
+}  // namespace
+
+int gpc_hip_track_stream_create(gpc_hip_ctx* c, int W, int H, const gpc_settings* settings, int cap_per_pair, int track_cap,
+                                gpc_hip_track_stream** out) {
+  if (!c || !out) return GPC_E_INVALID;
+  *out = nullptr;
+  CHK(gpc::trs_create_check(W, H, cap_per_pair, track_cap));
+  if (settings) CHK(check_settings(settings));
+  HIPCHK(c, hipSetDevice(c->device));
+  gpc_hip_track_stream* s = new gpc_hip_track_stream();
+  s->book.W = W, s->book.H = H, s->book.cap = cap_per_pair, s->book.track_cap = track_cap;
+  if (settings) s->settings = *settings, s->have_settings = true;
+  const size_t cap = (size_t)cap_per_pair;
+  if (hipMalloc((void**)&s->crec, pad16(sizeof(gpc::TrRec) * cap)) != hipSuccess ||
+      hipMalloc((void**)&s->cid, pad16(sizeof(int32_t) * cap)) != hipSuccess || hipMalloc((void**)&s->words, 16) != hipSuccess ||
+      hipMalloc((void**)&s->table, sizeof(gpc_track) * (size_t)(track_cap > 0 ? track_cap : 1)) != hipSuccess ||
+      hipMemsetAsync(s->words, 0, 16, c->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    snprintf(c->err, sizeof(c->err), "track stream of %d records per pair and %d rows: device allocation failed", cap_per_pair, track_cap);
+    trs_free(s);
+    return GPC_E_HIP;
+  }
+  c->track_streams.push_back(s);
+  *out = s;
+  return GPC_OK;
+}
+
+int gpc_hip_track_stream_destroy(gpc_hip_ctx* c, gpc_hip_track_stream* s) {
+  CHK(trs_check(c, s));
+  (void)hipSetDevice(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  for (size_t k = 0; k < c->track_streams.size(); ++k)
+    if (c->track_streams[k] == s) { c->track_streams.erase(c->track_streams.begin() + k); break; }
+  trs_free(s);
+  return GPC_OK;
+}
+
+int gpc_hip_track_stream_reset(gpc_hip_ctx* c, gpc_hip_track_stream* s) {
+  CHK(trs_check(c, s));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemsetAsync(s->words, 0, 16, c->stream));  // (behind whatever a push has queued)
+  gpc::trs_reset(s->book);
+  return GPC_OK;
+}
+
+int gpc_hip_track_stream_push_device(gpc_hip_ctx* c, gpc_hip_track_stream* s, const uint8_t* d_frames, int nframes,
+                                     gpc_correspondence* d_corr, int32_t* d_counts, int32_t* d_ncand, int32_t* d_prev,
+                                     int32_t* d_track_id, int* npairs) {
+  if (!d_frames || !d_corr || !d_counts || !d_prev || !d_track_id || !npairs) return GPC_E_INVALID;
+  gpc::TrsPush p;
+  CHK(trs_frames_usable(c, s, nframes, &p));
+  const int st = trs_push_frames(c, s, d_frames, nframes, d_corr, d_counts, d_ncand, d_prev, d_track_id, p);
+  if (st == GPC_OK || st == GPC_E_CAPACITY) *npairs = p.k;
+  return st;
+}
+
+int gpc_hip_track_stream_push_records_device(gpc_hip_ctx* c, gpc_hip_track_stream* s, const gpc_correspondence* d_corr,
+                                             const int32_t* d_counts, int npairs, int32_t* d_prev, int32_t* d_track_id) {
+  if (!d_corr || !d_counts || !d_prev || !d_track_id) return GPC_E_INVALID;
+  CHK(trs_check(c, s));
+  gpc::TrsPush p;
+  CHK(gpc::trs_plan(s->book, gpc::TRS_RECORDS, npairs, c->code_gen, &p));
+  HIPCHK(c, hipSetDevice(c->device));
+  CHK(trs_link(c, s, d_corr, d_counts, p, d_prev, d_track_id));
+  gpc::trs_commit(s->book, gpc::TRS_RECORDS, npairs, c->code_gen, p);
+  return GPC_OK;
+}
+
+// Host frames in, the new pairs' records, links and ids out: one device block (Stage), the device form once over it.
+int gpc_hip_track_stream_push(gpc_hip_ctx* c, gpc_hip_track_stream* s, const uint8_t* frames, int nframes, gpc_correspondence* corr,
+                              int32_t* counts, int32_t* ncand, int32_t* prev, int32_t* track_id, int* npairs, int32_t* n_tracks) {
+  if (!frames || !corr || !counts || !prev || !track_id || !npairs || !n_tracks) return GPC_E_INVALID;
+  gpc::TrsPush p;
+  CHK(trs_frames_usable(c, s, nframes, &p));
+  CHK(host_call_begin(c));
+  const int cap = s->book.cap, k = p.k;
+  const size_t n = (size_t)s->book.W * s->book.H, rec = (size_t)k * cap;
+  Stage st(c);
+  const size_t r_in = st.in(n * nframes), r_corr = st.out(sizeof(gpc_correspondence) * rec), r_cnt = st.out(sizeof(int32_t) * (size_t)k),
+               r_nc = st.out(sizeof(int32_t) * (size_t)nframes), r_prev = st.out(sizeof(int32_t) * rec),
+               r_id = st.out(sizeof(int32_t) * rec);
+  CHK(st.alloc(sizeof(int32_t) * ((size_t)k + nframes + 1)));  // counts [k], candidates [nframes], the number of tracks
+  CHK(st.up(r_in, frames, n * nframes));
+  int status = trs_push_frames(c, s, st.p(r_in), nframes, (gpc_correspondence*)st.p(r_corr), (int32_t*)st.p(r_cnt),
+                               (int32_t*)st.p(r_nc), (int32_t*)st.p(r_prev), (int32_t*)st.p(r_id), p);
+  if (status != GPC_OK && status != GPC_E_CAPACITY) return status;
+  status = GPC_OK;
+  int32_t* hc = c->h_cnt;
+  if (k) CHK(st.down(hc, r_cnt, sizeof(int32_t) * (size_t)k));
+  CHK(st.down(hc + k, r_nc, sizeof(int32_t) * (size_t)nframes));
+  HIPCHK(c, hipMemcpyAsync(hc + k + nframes, s->words + 1, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  CHK(st.wait());
+  for (int t = 0; t < k; ++t) {
+    const size_t m = (size_t)valid_records(hc[t], cap), at = (size_t)t * cap;
+    if (hc[t] > cap) status = GPC_E_CAPACITY;
+    if (!m) continue;
+    CHK(st.down(corr + at, r_corr + sizeof(gpc_correspondence) * at, sizeof(gpc_correspondence) * m));
+    CHK(st.down(prev + at, r_prev + sizeof(int32_t) * at, sizeof(int32_t) * m));
+    CHK(st.down(track_id + at, r_id + sizeof(int32_t) * at, sizeof(int32_t) * m));
+  }
+  CHK(st.wait());
+  memcpy(counts, hc, sizeof(int32_t) * (size_t)k);
+  if (ncand) memcpy(ncand, hc + k, sizeof(int32_t) * (size_t)nframes);
+  *n_tracks = hc[k + nframes];
+  gpc::trs_tighten(s->book, *n_tracks);
+  *npairs = k;
+  CHK(check_join_err(c));
+  return status;
+}
+
+int gpc_hip_track_stream_state(gpc_hip_ctx* c, gpc_hip_track_stream* s, int* frames_seen, int* pairs_seen, int32_t* n_tracks) {
+  CHK(trs_check(c, s));
+  HIPCHK(c, hipSetDevice(c->device));
+  int32_t total = 0;
+  CHK(trs_total(c, s, &total));
+  if (frames_seen) *frames_seen = s->book.frames_seen;
+  if (pairs_seen) *pairs_seen = s->book.pairs_seen;
+  if (n_tracks) *n_tracks = total;
+  return GPC_OK;
+}
+
+int gpc_hip_track_stream_table(gpc_hip_track_stream* s, const gpc_track** d_tracks, const int32_t** d_ntracks) {
+  if (!s || !d_tracks || !d_ntracks) return GPC_E_INVALID;
+  *d_tracks = s->table;
+  *d_ntracks = s->words + 1;
+  return GPC_OK;
+}
+
+int gpc_hip_track_stream_read_tracks(gpc_hip_ctx* c, gpc_hip_track_stream* s, int first, int n, gpc_track* out, int32_t* n_tracks) {
+  CHK(trs_check(c, s));
+  if (!n_tracks || (n > 0 && !out)) return GPC_E_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  int32_t total = 0;
+  CHK(trs_total(c, s, &total));
+  *n_tracks = total;
+  CHK(gpc::trs_read_check(s->book, first, n));
+  const long end = (long)first + n < total ? (long)first + n : total;  // rows at total and beyond do not exist yet
+  if (end > first) HIPCHK(c, hipMemcpy(out, s->table + first, sizeof(gpc_track) * (size_t)(end - first), hipMemcpyDeviceToHost));
+  return GPC_OK;
 }
 
 // ------------------------------------------------------------------ match filtering: grid motion consensus
