@@ -726,16 +726,83 @@ int gpc_hip_consensus_correspondences(gpc_hip_ctx* ctx, const gpc_correspondence
                                       int width, int height, int npairs, const gpc_consensus* prm, uint8_t* keep,
                                       gpc_correspondence* out, int cap_out, int32_t* index, int32_t* out_counts);
 
+/* ---- match refinement: sub-pixel position and photometric cost ------------------------ */
+/* A unique-code collision says which pixel matches, not how well or where between pixels.  These calls compare the image
+ * windows around the two ends of every match: the sum of absolute differences is the match's cost (a confidence), and the
+ * costs at the neighbouring target positions give a parabola whose minimum is the sub-pixel position.  The reference has no
+ * counterpart: the rule is this library's own, made of integers only, so every implementation of it gives the same bytes.
+ * In a chain refinement comes after the consensus filter (which needs whole d) and before scoring.
+ *
+ * Input: P = npairs lists rec[t][0 .. m_t), m_t = min(max(counts[t], 0), cap_per_pair); 8-bit images imgL[P][height][width]
+ *   and imgR[P][height][width] (whatever the caller passes, raw or smoothed; the sequence form uses frames t and t + 1 of one
+ *   [nframes][height][width] array); a radius r, 1 <= r <= 6.  Any width, height >= 1.
+ *   Source and target as in the consensus filter: (src_x, src_y) -> (tar_x, tar_y) of a correspondence; (x, y) ->
+ *     (x - (int)d, y) of a support, whose d must be finite, d == truncf(d) and |d| < 2^24, or the record is not evaluated.
+ *   cost(sx, sy) = sum over |i| <= r, |j| <= r of |imgL[y + j][x + i] - imgR[ty + sy + j][tx + sx + i]|, at most
+ *     169 * 255 = 43 095.  Supports use the shifts (-1, 0), (0, 0), (+1, 0); correspondences also (0, -1) and (0, +1).
+ *   A record is EVALUATED iff every pixel of every window it needs lies inside the image (the target's window with its
+ *     shifts: +-1 in x for supports, in x and y for correspondences).  One that is not gets {0, 0, 0xFFFF, 0}.
+ *   Per axis, with c-, c0, c+ the costs at the target's shifts -1, 0, +1: a = c- + c+ - 2 c0, n = c- - c+.  The axis HAS A
+ *     MINIMUM iff c0 <= c-, c0 <= c+ and a > 0 (then |n| <= a), and the target's sub-pixel shift in 1/256 pixel is
+ *     q = sgn(n) * ((256 |n| + a) div (2 a)): rounded half away from zero, |q| <= 128.  Otherwise q = 0 and the axis flag
+ *     stays clear: the integer position is no local photometric minimum, which is itself a verification signal.
+ * Output: one gpc_refinement per record; cost = c0; flags bit 0 evaluated, bit 1 minimum in x, bit 2 minimum in y.
+ *   Supports have dy_q8 = 0 and never bit 2.  The refined target is (tx + dx_q8 / 256, ty + dy_q8 / 256).  For supports,
+ *   `out` (optional) receives {x, y, d - (float)dx_q8 * 0.00390625f} (one float32 subtraction of an exact product; a record
+ *   that is not evaluated is copied unchanged): an array gpc_hip_score_supports_device takes as it is.  Entries at i >= m_t
+ *   of every output are left untouched.  Nothing is thresholded or compacted.
+ * GPC_E_INVALID: r out of range, null required pointers, npairs < 1, cap_per_pair < 1, width or height < 1, `out`
+ * overlapping the input records.  GPC_E_UNSUPPORTED: npairs > 65535, npairs * cap_per_pair > 2^31 - 1,
+ * width * height > 2^30. */
+typedef struct gpc_refinement {
+  int16_t dx_q8, dy_q8; /* the target's sub-pixel shift in 1/256 pixel, -128 .. 128 */
+  uint16_t cost;        /* c0; 0xFFFF when the record is not evaluated               */
+  uint16_t flags;       /* bit 0 evaluated, bit 1 minimum in x, bit 2 minimum in y   */
+} gpc_refinement;
+/* Records and images already on the device: d_rec and d_ref (and d_out, which may be NULL) [npairs][cap_per_pair],
+ * d_counts[npairs] (read on the device), d_imgL and d_imgR [npairs][height][width].  Pure functions of their arguments: no
+ * forest is needed, and the calls only queue one launch on the context's stream; no workspace. */
+int gpc_hip_refine_supports_device(gpc_hip_ctx* ctx, const gpc_support* d_rec, int cap_per_pair, const int32_t* d_counts,
+                                   const uint8_t* d_imgL, const uint8_t* d_imgR, int width, int height, int npairs, int radius,
+                                   gpc_refinement* d_ref, gpc_support* d_out);
+int gpc_hip_refine_correspondences_device(gpc_hip_ctx* ctx, const gpc_correspondence* d_rec, int cap_per_pair,
+                                          const int32_t* d_counts, const uint8_t* d_imgL, const uint8_t* d_imgR, int width,
+                                          int height, int npairs, int radius, gpc_refinement* d_ref);
+/* Match and refine: gpc_hip_match_batch_device / gpc_hip_match_sequence_device exactly as they are -- into the caller's
+ * d_supports / d_corr, d_counts and d_ncand (optional), with their settings, refusals, statuses and waiting; with two lanes
+ * (gpc_hip_set_pipeline(ctx, 2)) the lanes are drained and the call runs on the context's stream -- then the refinement of
+ * what they wrote, over the raw images (frames t and t + 1 for pair t of a sequence).  Group mode: the batch form refines
+ * the union; the sequence form is GPC_E_UNSUPPORTED, as the sequence itself. */
+int gpc_hip_refine_batch_device(gpc_hip_ctx* ctx, const uint8_t* d_rawL, const uint8_t* d_rawR, int width, int height,
+                                int npairs, const gpc_settings* settings, int radius, gpc_support* d_supports, int cap_per_pair,
+                                int32_t* d_counts, int32_t* d_ncand, gpc_refinement* d_ref, gpc_support* d_out);
+int gpc_hip_refine_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int width, int height, int nframes,
+                                   const gpc_settings* settings, int radius, gpc_correspondence* d_corr, int cap_per_pair,
+                                   int32_t* d_counts, int32_t* d_ncand, gpc_refinement* d_ref);
+/* Host records, counts, images and outputs through the records forms; synchronous, in chunks of at most 16 pairs, pageable
+ * arrays through the context's page-locked arena.  Each pair's first m_t records travel; what comes back equals the device
+ * forms byte for byte, untouched entries included. */
+int gpc_hip_refine_supports(gpc_hip_ctx* ctx, const gpc_support* rec, int cap_per_pair, const int32_t* counts,
+                            const uint8_t* imgL, const uint8_t* imgR, int width, int height, int npairs, int radius,
+                            gpc_refinement* ref, gpc_support* out);
+int gpc_hip_refine_correspondences(gpc_hip_ctx* ctx, const gpc_correspondence* rec, int cap_per_pair, const int32_t* counts,
+                                   const uint8_t* imgL, const uint8_t* imgR, int width, int height, int npairs, int radius,
+                                   gpc_refinement* ref);
+
 /* ---- measurement -------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the context's stream.  When enabled every launch of
  * the named kernels is bracketed by hipEvents; gpc_hip_kernel_time returns the summed
  * milliseconds and launch count since the last reset (synchronises the stream). */
 int gpc_hip_enable_kernel_timing(gpc_hip_ctx* ctx, int enable);
 /* Restrict the bracketing to the kernels whose index bit is set (default: all).  Every pair of
- * event records costs a little stream time, so a benchmark times only the kernel it reports. */
+ * event records costs a little stream time, so a benchmark times only the kernel it reports.  The mask has 32 bits and
+ * gpc_hip_kernel_count() is the number of slots it addresses (at most 32).  gpc_hip_kernel_slots() counts every slot:
+ * those from gpc_hip_kernel_count() on (k_refine) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
+ * gpc_hip_kernel_launch_name and gpc_hip_kernel_time take their indices like any other. */
 int gpc_hip_set_kernel_timing_mask(gpc_hip_ctx* ctx, unsigned mask);
 int gpc_hip_reset_kernel_timing(gpc_hip_ctx* ctx);
 int gpc_hip_kernel_count(void);
+int gpc_hip_kernel_slots(void);
 const char* gpc_hip_kernel_name(int index);
 /* The profiler's (rocprofv3) name of the template instantiation this context last launched under timing slot
  * `index`, e.g. "gpc::k_row_join<4, 256, false>"; "" before the first launch.

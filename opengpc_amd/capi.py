@@ -29,6 +29,8 @@ SCORE_DTYPE = np.dtype([("n_records", "<i8"), ("n_ignored", "<i8"), ("n_no_truth
                         ("n_matchable", "<i8")])
 # gpc_track: one row per track (gpc_hip_track_*)
 TRACK_DTYPE = np.dtype([("first_pair", "<i4"), ("first_record", "<i4"), ("length", "<i4"), ("last_record", "<i4")])
+# gpc_refinement: one per record (gpc_hip_refine_*); flags bit 0 evaluated, bit 1 minimum in x, bit 2 minimum in y
+REFINEMENT_DTYPE = np.dtype([("dx_q8", "<i2"), ("dy_q8", "<i2"), ("cost", "<u2"), ("flags", "<u2")])
 
 
 class Settings(C.Structure):
@@ -98,7 +100,7 @@ SYMBOLS = [
     "gpc_hip_hash_codes", "gpc_hip_rectified_match", "gpc_hip_stereo_match",
     "gpc_hip_match_pair", "gpc_hip_match_batch_device", "gpc_hip_set_pipeline", "gpc_hip_pipeline_join", "gpc_hip_match_batch",
     "gpc_hip_match_batch_device_packed", "gpc_hip_match_batch_packed", "gpc_hip_expand_packed", "gpc_hip_host_threads", "gpc_hip_host_numa_node", "gpc_hip_batch_stages", "gpc_hip_host_worker_cpus", "gpc_hip_fed_calls",
-    "gpc_hip_enable_kernel_timing", "gpc_hip_set_kernel_timing_mask", "gpc_hip_reset_kernel_timing", "gpc_hip_kernel_count",
+    "gpc_hip_enable_kernel_timing", "gpc_hip_set_kernel_timing_mask", "gpc_hip_reset_kernel_timing", "gpc_hip_kernel_count", "gpc_hip_kernel_slots",
     "gpc_hip_kernel_name", "gpc_hip_kernel_launch_name", "gpc_hip_kernel_time",
     "gpc_hip_train_set_create", "gpc_hip_train_set_destroy", "gpc_hip_train_set_size", "gpc_hip_train_set_marks",
     "gpc_hip_train_eval_split", "gpc_hip_train_mark_split_samples", "gpc_hip_train_fern",
@@ -114,6 +116,8 @@ SYMBOLS = [
     "gpc_hip_track_stream_create", "gpc_hip_track_stream_destroy", "gpc_hip_track_stream_reset",
     "gpc_hip_track_stream_push_device", "gpc_hip_track_stream_push", "gpc_hip_track_stream_push_records_device",
     "gpc_hip_track_stream_state", "gpc_hip_track_stream_table", "gpc_hip_track_stream_read_tracks",
+    "gpc_hip_refine_supports_device", "gpc_hip_refine_correspondences_device", "gpc_hip_refine_batch_device",
+    "gpc_hip_refine_sequence_device", "gpc_hip_refine_supports", "gpc_hip_refine_correspondences",
 ]
 
 
@@ -215,6 +219,15 @@ def load():
                                                  C.POINTER(Consensus), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gpc_hip_consensus_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings),
                                                     C.POINTER(Consensus), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_refine_supports_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                 C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.gpc_hip_refine_supports.argtypes = L.gpc_hip_refine_supports_device.argtypes
+    L.gpc_hip_refine_correspondences_device.argtypes = L.gpc_hip_refine_supports_device.argtypes[:11]
+    L.gpc_hip_refine_correspondences.argtypes = L.gpc_hip_refine_correspondences_device.argtypes
+    L.gpc_hip_refine_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings),
+                                              C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_refine_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gpc_hip_match_batch_device_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(Settings), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                     C.c_void_p]
@@ -904,6 +917,66 @@ class Context:
         self._ck(st, allow=(E_CAPACITY,))
         return keep, out, index, out_counts, st
 
+    # ---- match refinement (gpc_hip_refine_*): sub-pixel position and photometric cost of every record
+    def refine_records_device(self, d_rec, corr, cap_per_pair, d_counts, d_imgL, d_imgR, width, height, npairs, radius, d_ref,
+                              d_out=0):
+        """Records [npairs][cap_per_pair] (corr: CORR_DTYPE, else SUPPORT_DTYPE) and 8-bit images [npairs][height][width]
+        already in HBM -> d_ref [npairs][cap_per_pair] of REFINEMENT_DTYPE and, for supports, d_out (optional) the records with
+        the refined d; asynchronous, no forest needed.  Pointers are integers."""
+        if corr:
+            if d_out:
+                raise ValueError("d_out: supports only")
+            self._ck(self.L.gpc_hip_refine_correspondences_device(
+                self.h, C.c_void_p(d_rec), int(cap_per_pair), C.c_void_p(d_counts), C.c_void_p(d_imgL), C.c_void_p(d_imgR),
+                int(width), int(height), int(npairs), int(radius), C.c_void_p(d_ref)))
+        else:
+            self._ck(self.L.gpc_hip_refine_supports_device(
+                self.h, C.c_void_p(d_rec), int(cap_per_pair), C.c_void_p(d_counts), C.c_void_p(d_imgL), C.c_void_p(d_imgR),
+                int(width), int(height), int(npairs), int(radius), C.c_void_p(d_ref), C.c_void_p(d_out or 0)))
+
+    def refine_batch_device(self, d_rawL, d_rawR, width, height, npairs, settings, radius, d_supports, cap_per_pair, d_counts,
+                            d_ncand, d_ref, d_out=0):
+        """match_batch_device into d_supports / d_counts / d_ncand, then the refinement of what it wrote over the raw images."""
+        self._ck(self.L.gpc_hip_refine_batch_device(self.h, C.c_void_p(d_rawL), C.c_void_p(d_rawR), int(width), int(height),
+                                                    int(npairs), C.byref(settings), int(radius), C.c_void_p(d_supports),
+                                                    int(cap_per_pair), C.c_void_p(d_counts), C.c_void_p(d_ncand or 0),
+                                                    C.c_void_p(d_ref), C.c_void_p(d_out or 0)))
+
+    def refine_sequence_device(self, d_frames, width, height, nframes, settings, radius, d_corr, cap_per_pair, d_counts, d_ncand,
+                               d_ref):
+        """match_sequence_device into d_corr / d_counts / d_ncand, then the refinement over frames t and t + 1."""
+        self._ck(self.L.gpc_hip_refine_sequence_device(self.h, C.c_void_p(d_frames), int(width), int(height), int(nframes),
+                                                       C.byref(settings), int(radius), C.c_void_p(d_corr), int(cap_per_pair),
+                                                       C.c_void_p(d_counts), C.c_void_p(d_ncand or 0), C.c_void_p(d_ref)))
+
+    def refine_records(self, records, counts, imgL, imgR, radius=3, ref=None, out=None):
+        """Host records [P, cap] (SUPPORT_DTYPE or CORR_DTYPE), their true counts [P] and host images [P, H, W] uint8 ->
+        (ref [P, cap] of REFINEMENT_DTYPE, out [P, cap] supports with the refined d, or None for correspondences).  Entries
+        beyond min(counts[t], cap) are left as they were (zero in arrays made here)."""
+        records = np.asarray(records)
+        if records.dtype not in (SUPPORT_DTYPE, CORR_DTYPE) or records.ndim != 2 or records.shape[1] < 1 or records.shape[0] < 1:
+            raise ValueError("records: [P, cap] of SUPPORT_DTYPE or CORR_DTYPE")
+        corr = records.dtype == CORR_DTYPE
+        if not records.flags.c_contiguous:
+            records = np.ascontiguousarray(records)
+        counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+        imgL, imgR = _host_frames(imgL), _host_frames(imgR)
+        P, cap = records.shape
+        if imgL.ndim != 3 or imgL.shape != imgR.shape or imgL.shape[0] != P or len(counts) != P:
+            raise ValueError("counts [P] and images [P, H, W] of one shape for P = %d pairs" % P)
+        _, H, W = imgL.shape
+        ref = ref if ref is not None else np.zeros((P, cap), REFINEMENT_DTYPE)
+        if corr:
+            if out is not None:
+                raise ValueError("out: supports only")
+            self._ck(self.L.gpc_hip_refine_correspondences(self.h, _ptr(records), cap, _ptr(counts), _ptr(imgL), _ptr(imgR), W, H, P,
+                                                           int(radius), _ptr(ref)))
+            return ref, None
+        out = out if out is not None else np.zeros((P, cap), SUPPORT_DTYPE)
+        self._ck(self.L.gpc_hip_refine_supports(self.h, _ptr(records), cap, _ptr(counts), _ptr(imgL), _ptr(imgR), W, H, P,
+                                                int(radius), _ptr(ref), _ptr(out)))
+        return ref, out
+
     # ---- fern training: the scoring loop
     def train_set(self, triplets):
         """Uploads (n, 3, 729) uint8 patch triplets (ref, pos, neg); returns a TrainSet."""
@@ -959,10 +1032,11 @@ class Context:
         """HIP-event bracketing of kernel launches; `only` = iterable of kernel names to restrict it to."""
         mask = 0xFFFFFFFF
         if only is not None:
-            names = [self.L.gpc_hip_kernel_name(i).decode() for i in range(self.L.gpc_hip_kernel_count())]
+            names = [self.L.gpc_hip_kernel_name(i).decode() for i in range(self.L.gpc_hip_kernel_slots())]
             mask = 0
             for n in only:
-                mask |= 1 << names.index(n)
+                if names.index(n) < 32:     # (the slots behind the mask are always bracketed)
+                    mask |= 1 << names.index(n)
         self._ck(self.L.gpc_hip_set_kernel_timing_mask(self.h, mask))
         self._ck(self.L.gpc_hip_enable_kernel_timing(self.h, int(on)))
 
@@ -972,12 +1046,12 @@ class Context:
     def kernel_launch_names(self):
         """{timing slot name: rocprofv3 name of the instantiation last launched there}"""
         return {self.L.gpc_hip_kernel_name(i).decode(): self.L.gpc_hip_kernel_launch_name(self.h, i).decode()
-                for i in range(self.L.gpc_hip_kernel_count())}
+                for i in range(self.L.gpc_hip_kernel_slots())}
 
     def kernel_times(self):
         """{kernel name: (total ms, launches)} since the last reset."""
         out = {}
-        for i in range(self.L.gpc_hip_kernel_count()):
+        for i in range(self.L.gpc_hip_kernel_slots()):
             ms, n = C.c_float(), C.c_int()
             self._ck(self.L.gpc_hip_kernel_time(self.h, i, C.byref(ms), C.byref(n)))
             out[self.L.gpc_hip_kernel_name(i).decode()] = (ms.value, n.value)
