@@ -6,7 +6,7 @@ import subprocess
 
 import pytest
 
-from forest_groups_util import forest_text, group_texts
+from forest_groups_util import PLANE_FIRST, TAU_RULES, TAU_VALUES, fern_split, forest_text, group_texts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FORESTS = {k: os.path.join(ROOT, "forests", f) for k, f in
@@ -49,6 +49,8 @@ def test_groups_of_committed_forests(oracle, name, W, H):
     ([3, 70, 4], [3, 32, 32, 6, 4]),
     ([0, 7, 0, 25], [32]),
     ([32, 32], [32, 32]),
+    ([32, 5, 1, 20, 7, 9], [32, 26, 16]),   # the unequal groups of test_gpu_forest_shapes.py
+    ([40, 3], [32, 8, 3]),
 ])
 def test_packing_rule(oracle, sizes, want):
     import opengpc_amd as g
@@ -115,3 +117,21 @@ def test_new_kernels_use_no_scratch():
     for r in rows:
         m = re.search(r"spill s +\d+ v +(\d+) +scratch +(\d+)", r)
         assert m and m.group(1) == "0" and m.group(2) == "0", r
+
+
+def test_forest_text_rules():
+    """forest_text as test_gpu_forest_shapes.py uses it: where the rules put the zeros, the values, the ferns' scales, the split
+    and -128 on the last test that is kept"""
+    for T in (1, 9, 26, 33):
+        for rule in TAU_RULES:
+            tok = forest_text(fern_split(T, "each"), seed=T, tau=rule, scales="sml").split()
+            taus = [int(tok[1 + 9 * i + 8]) for i in range(T)]
+            zero = {"zero": lambda s: True, "nonzero": lambda s: False, "plane_first": lambda s: s not in PLANE_FIRST,
+                    "plane_rest": lambda s: s in PLANE_FIRST, "alternating": lambda s: s % 2 == 1}[rule]
+            assert all((t == 0) == zero(s) and (t == 0 or t in TAU_VALUES) for s, t in enumerate(taus)), (T, rule)
+            assert [tok[1 + 9 * i + 1] for i in range(T)] == ["sml"[i % 3] for i in range(T)]
+    assert fern_split(9, 1) == [9] and fern_split(9, 2) == [5, 4] and fern_split(3, "each") == [1, 1, 1]
+    # the texts the generator gave before it knew rules and scales, literally
+    assert forest_text([2, 1], seed=2) == "2\n0 l 2\n0 9 -6 -11 -5 -4\n1 8 -1 -11 -4 4\n1 l 1\n0 8 6 13 -8 16\n"
+    assert forest_text([2], seed=3, tau=False) == "1\n0 l 2\n0 8 -11 -9 -7 0\n1 -9 8 10 2 0\n"
+    assert forest_text([20, 20], tau="alternating", m128_last=True).split("\n")[1 + 1 + 20 + 12].split()[-1] == "-128"
