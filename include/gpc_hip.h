@@ -242,7 +242,10 @@ int gpc_hip_match_fetch(gpc_hip_ctx* ctx, void* out, int cap, int* n_out, int* n
  * names the launch), and -- for callers that gave the context their own stream and wait on it themselves -- at the
  * top of the NEXT call that queues such a join and in gpc_hip_destroy (which then returns GPC_E_HIP after freeing
  * everything): such callers should call gpc_hip_synchronize once before trusting a batch they did not wait for
- * through this library. */
+ * through this library.
+ * A pair with more than cap_per_pair records: the call still returns GPC_OK (the counts stay on the device, the host
+ * never sees them); d_counts holds the true count, the pair's first cap_per_pair records are valid and nothing is written
+ * behind them -- compare d_counts with cap_per_pair after the wait. */
 int gpc_hip_match_batch_device(gpc_hip_ctx* ctx, const uint8_t* d_rawL, const uint8_t* d_rawR,
                                int width, int height, int npairs, const gpc_settings* settings,
                                gpc_support* d_out, int cap_per_pair, int32_t* d_counts,
@@ -294,7 +297,9 @@ int gpc_hip_host_numa_node(const gpc_hip_ctx* ctx);
  * Waiting is as for gpc_hip_match_batch_device: with epipolar_mode = 1 and use_hashtable = 0 the call only queues work on
  * the context's stream; the device-wide matchers (epipolar_mode = 0 or use_hashtable = 1) wait on the host once inside
  * the call.  The outputs may be read after gpc_hip_synchronize (or another wait on the stream).
- * A pair with more than cap_per_pair records: GPC_E_CAPACITY, true counts, each pair's first cap_per_pair records valid.
+ * A pair with more than cap_per_pair records: true counts, each pair's first cap_per_pair records valid, nothing written
+ * behind them; the device form returns GPC_OK as gpc_hip_match_batch_device does (compare d_counts with cap_per_pair after
+ * the wait), the host form below GPC_E_CAPACITY.
  * nframes < 2, null pointers or a bad size: GPC_E_INVALID; no forest: GPC_E_NO_FOREST; group mode (ngroups > 1):
  * GPC_E_UNSUPPORTED.  With two lanes (gpc_hip_set_pipeline(ctx, 2)) the lanes are drained and the call runs on the
  * context's stream. */

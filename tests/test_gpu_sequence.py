@@ -199,23 +199,41 @@ def test_equals_stereo_match(ctx, forest_paths):
 
 
 def test_capacity(ctx, oracle, forest_paths):
+    """A capacity of half the largest pair, every matcher.  The host form returns GPC_E_CAPACITY, the true counts and each
+    pair's first records.  The device form only queues work (the device-wide matchers wait for their plan, not for the
+    counts), so it returns GPC_OK and leaves the true counts in d_counts; it runs on outputs filled with 0xA5 that hold a
+    spare pair's worth of slots behind the last pair, a spare count and a spare candidate word, and every byte is compared:
+    the first min(count, cap) records of each pair, the fill in every other slot."""
+    import torch
     import opengpc_amd as g
+    from devicewide_util import FILL32, compare, corr_words, expected, filled
     W, H, N = 176, 67, 4
     frames = frames_of(W, H, N, 21)
     ctx.load_forest(forest_paths["zero"], W, H)
     rc, f = oracle.read_forest(forest_paths["zero"], W, H)
-    for epipolar, hashtable in ((True, False), (False, True)):
+    dev = torch.device("cuda", 0)
+    d_f = torch.from_numpy(frames).to(dev)
+    for epipolar, hashtable in MATCHERS:
+        s = settings(epipolar, hashtable)
         want, ncw = oracle_sequence(oracle, frames, f, epipolar, hashtable)
         cap = max(len(w) for w in want) // 2
         assert cap > 10
-        out, cnt, nc, st = ctx.match_sequence(frames, settings(epipolar, hashtable), cap)
+        out, cnt, nc, st = ctx.match_sequence(frames, s, cap)
         assert st == g.capi.E_CAPACITY and list(cnt) == [len(w) for w in want] and list(nc) == ncw
-        rec, dcnt, dnc = run_device(ctx, frames, settings(epipolar, hashtable), cap)
-        assert list(dcnt) == list(cnt)
+        d_out, d_cnt, d_nc = filled(N * cap * 16, dev), filled(N * 4, dev), filled((N + 1) * 4, dev)
+        torch.cuda.synchronize(dev)
+        st = ctx.L.gpc_hip_match_sequence_device(ctx.h, d_f.data_ptr(), W, H, N, s, d_out.data_ptr(), cap, d_cnt.data_ptr(), d_nc.data_ptr())
+        assert st == 0, (epipolar, hashtable, st)
+        ctx.synchronize()
+        dcnt, dnc = d_cnt.cpu().numpy().view(np.int32), d_nc.cpu().numpy().view(np.int32)
+        assert list(dcnt[:N - 1]) == list(cnt) and list(dnc[:N]) == ncw
+        assert dcnt[N - 1:].view(np.uint32) == FILL32 and dnc[N:].view(np.uint32) == FILL32, "a count behind the sequence's was written"
+        words = [corr_words(w) for w in want]
+        compare(d_out.cpu().numpy().view(np.uint32).reshape(N, cap, 4), expected(words, cap), words,
+                "epipolar %d, hash table %d, cap %d" % (epipolar, hashtable, cap))
         for t in range(N - 1):
             k = min(cap, len(want[t]))
             same_corr(out[t, :k], want[t][:k], t)
-            same_corr(rec[t, :k], want[t][:k], t)
 
 
 def test_refusals(oracle, forest_paths):
