@@ -794,6 +794,83 @@ int gpc_hip_refine_correspondences(gpc_hip_ctx* ctx, const gpc_correspondence* r
                                    const uint8_t* imgL, const uint8_t* imgR, int width, int height, int npairs, int radius,
                                    gpc_refinement* ref);
 
+/* ---- matching over an image pyramid ---------------------------------------------------- */
+/* The matchers see a 27x27 window at one resolution.  These calls run them on every level of an image pyramid and merge
+ * what the levels find into one record list in level 0's coordinates: texture coarser than the window, and motion beyond
+ * disp_high, show at a coarser level.  The fern tests are offsets within the patch, so the same forest applies at every
+ * level: level l sees a 27 * 2^l window of the original image.  The reference has no pyramid: the rules are this library's
+ * own, made of integers only, so that every implementation of them gives the same bytes.
+ *
+ * Levels: 1 <= levels <= GPC_MAX_PYRAMID_LEVELS.  Level 0 is the input; level l has W_l = W >> l and H_l = H_{l-1} / 2
+ *   rounded down (an odd last row is dropped).  Every level must be an image the library takes today (W_l % 16 == 0,
+ *   W_l >= 42, H_l >= 30), else GPC_E_INVALID: 3 levels need W % 64 == 0, W >= 192, H >= 120.
+ * Downsampling: level l's raw image is the 2x2 mean of level l-1's raw image, out[y][x] = (a + b + c + d + 2) >> 2 over
+ *   in[2y .. 2y+1][2x .. 2x+1].  Each level is then preprocessed and hashed exactly as an image of its own size is by
+ *   gpc_hip_match_batch_device / gpc_hip_match_sequence_device (box and Sobel on that level's raw image).
+ * Settings of level l: gradient_threshold, epipolar_mode and use_hashtable unchanged; disp_high_l = disp_high >> l,
+ *   vertical_tolerance_l = vertical_tolerance >> l, so a mapped record never exceeds the caller's bounds.
+ * Mapping: a level-l support (x, y, d) becomes (x << l, y << l, d * 2^l) (the float stays exact); a correspondence has all
+ *   four coordinates shifted left by l.  A level-l pixel is the 2^l x 2^l BLOCK of level-0 pixels [x << l, (x << l) + 2^l) x
+ *   [y << l, (y << l) + 2^l); the block's TOP-LEFT CORNER stands for the block, so a coarse record carries up to 2^l - 1
+ *   pixels of position it does not resolve.
+ * Merge, per pair: level 0's records come first, all of them, in the matcher's order.  Then, for l = 1 .. levels-1 in
+ *   turn, level l's mapped records in the matcher's order, a record being kept if and only if its source block holds the
+ *   (mapped) source pixel of no record kept from levels < l.  Records of one level never suppress each other; a kept
+ *   level-l record does suppress levels > l.  A level-l record whose source lies outside [0, W >> l) x [0, H >> l) (only
+ *   records a caller constructs) has no block: it is kept and suppresses nothing.
+ * Capacity: the merge is decided on all records, never on the capped ones.  d_counts[npairs] holds the true totals,
+ *   d_level_counts[levels][npairs] the true kept counts per level (their sum is the total; they recover each record's
+ *   level), d_ncand (optional) the candidate counts of every level, [levels][npairs][2] for pairs and [levels][nframes] for
+ *   frames.  A pair's first min(count, cap_per_pair) records are valid and nothing is written behind them.  The device forms
+ *   return GPC_OK, the host forms GPC_E_CAPACITY, as gpc_hip_match_batch_device and gpc_hip_match_sequence do.
+ * levels == 1: byte for byte what gpc_hip_match_batch_device / gpc_hip_match_sequence_device write; d_level_counts equals
+ *   d_counts.
+ * Every matcher (epipolar_mode 0 / 1 x use_hashtable 0 / 1) and either arithmetic is taken: the match of a level is the
+ *   existing one, with its waiting (the device-wide matchers wait on the host once per level).  Refusals: group mode with
+ *   more than one group GPC_E_UNSUPPORTED; no forest GPC_E_NO_FOREST; a forest whose size is not width x height (level 0)
+ *   GPC_E_INVALID; more than 65535 pairs GPC_E_UNSUPPORTED.  With two lanes (gpc_hip_set_pipeline(ctx, 2)) the lanes are
+ *   drained and the call runs on the context's stream.  After a call the context's forest, its size and the generation of
+ *   its codes are what they were: a plain match at width x height needs no gpc_hip_set_forest, and a track stream hashed
+ *   before the call still takes frames.
+ * Workspaces of the context, grown on demand: the raw images of levels 1 .. levels-1 (a third of the input), every record
+ *   of every level ((W_l - 26) * (H_l - 26) + 1 per pair and level), one bit per pixel and pair, one bit per record slot. */
+#define GPC_MAX_PYRAMID_LEVELS 4
+/* Host only: the geometry check above; widths, heights (optional) receive `levels` entries each. */
+int gpc_hip_pyramid_levels(int width, int height, int levels, int32_t* widths, int32_t* heights);
+/* One downsampling step over d_src[nimages][height][width], writing d_dst[nimages][height / 2][width / 2].  width % 32 == 0,
+ * height >= 2, d_src 8-byte and d_dst 4-byte aligned (GPC_E_INVALID otherwise); nimages <= 65535.  Needs no forest;
+ * asynchronous on the context's stream. */
+int gpc_hip_pyramid_down_device(gpc_hip_ctx* ctx, const uint8_t* d_src, int width, int height, int nimages, uint8_t* d_dst);
+/* The merge alone, over records already on the device: d_rec, caps and d_cnt are HOST arrays of `levels` entries -- level
+ * l's records d_rec[l][npairs][caps[l]] (unmapped, as the matcher wrote them at level l), its capacity, and its counts
+ * d_cnt[l][npairs] (read on the device; min(max(count, 0), caps[l]) records are read).  width, height describe level 0 and
+ * may be any positive size.  Outputs as above.  Needs no forest; the calls only queue work on the context's stream (per
+ * level: test and count, scan, write and mark). */
+int gpc_hip_pyramid_merge_supports_device(gpc_hip_ctx* ctx, const gpc_support* const* d_rec, const int32_t* caps,
+                                          const int32_t* const* d_cnt, int width, int height, int npairs, int levels,
+                                          gpc_support* d_out, int cap_per_pair, int32_t* d_counts, int32_t* d_level_counts);
+int gpc_hip_pyramid_merge_correspondences_device(gpc_hip_ctx* ctx, const gpc_correspondence* const* d_rec, const int32_t* caps,
+                                                 const int32_t* const* d_cnt, int width, int height, int npairs, int levels,
+                                                 gpc_correspondence* d_out, int cap_per_pair, int32_t* d_counts,
+                                                 int32_t* d_level_counts);
+/* Match and merge: raw pairs (frames) in HBM as gpc_hip_match_batch_device (gpc_hip_match_sequence_device) takes them.
+ * Every frame of a sequence is downsampled, preprocessed and hashed once per level. */
+int gpc_hip_pyramid_batch_device(gpc_hip_ctx* ctx, const uint8_t* d_rawL, const uint8_t* d_rawR, int width, int height,
+                                 int npairs, int levels, const gpc_settings* settings, gpc_support* d_out, int cap_per_pair,
+                                 int32_t* d_counts, int32_t* d_level_counts, int32_t* d_ncand);
+int gpc_hip_pyramid_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int width, int height, int nframes, int levels,
+                                    const gpc_settings* settings, gpc_correspondence* d_out, int cap_per_pair,
+                                    int32_t* d_counts, int32_t* d_level_counts, int32_t* d_ncand);
+/* The same from / to host memory (pageable or page-locked), synchronous, in chunks of at most 16 pairs (16 frames;
+ * consecutive chunks of a sequence share one).  What comes back equals the device forms byte for byte; bytes of `out` the
+ * device form does not write stay as they were. */
+int gpc_hip_pyramid_batch(gpc_hip_ctx* ctx, const uint8_t* rawL, const uint8_t* rawR, int width, int height, int npairs,
+                          int levels, const gpc_settings* settings, gpc_support* out, int cap_per_pair, int32_t* counts,
+                          int32_t* level_counts, int32_t* ncand);
+int gpc_hip_pyramid_sequence(gpc_hip_ctx* ctx, const uint8_t* frames, int width, int height, int nframes, int levels,
+                             const gpc_settings* settings, gpc_correspondence* out, int cap_per_pair, int32_t* counts,
+                             int32_t* level_counts, int32_t* ncand);
+
 /* ---- measurement -------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the context's stream.  When enabled every launch of
  * the named kernels is bracketed by hipEvents; gpc_hip_kernel_time returns the summed
@@ -802,7 +879,7 @@ int gpc_hip_enable_kernel_timing(gpc_hip_ctx* ctx, int enable);
 /* Restrict the bracketing to the kernels whose index bit is set (default: all).  Every pair of
  * event records costs a little stream time, so a benchmark times only the kernel it reports.  The mask has 32 bits and
  * gpc_hip_kernel_count() is the number of slots it addresses (at most 32).  gpc_hip_kernel_slots() counts every slot:
- * those from gpc_hip_kernel_count() on (k_refine) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
+ * those from gpc_hip_kernel_count() on (k_refine, k_pyr_*) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
  * gpc_hip_kernel_launch_name and gpc_hip_kernel_time take their indices like any other. */
 int gpc_hip_set_kernel_timing_mask(gpc_hip_ctx* ctx, unsigned mask);
 int gpc_hip_reset_kernel_timing(gpc_hip_ctx* ctx);

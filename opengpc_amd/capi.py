@@ -118,6 +118,9 @@ SYMBOLS = [
     "gpc_hip_track_stream_state", "gpc_hip_track_stream_table", "gpc_hip_track_stream_read_tracks",
     "gpc_hip_refine_supports_device", "gpc_hip_refine_correspondences_device", "gpc_hip_refine_batch_device",
     "gpc_hip_refine_sequence_device", "gpc_hip_refine_supports", "gpc_hip_refine_correspondences",
+    "gpc_hip_pyramid_levels", "gpc_hip_pyramid_down_device", "gpc_hip_pyramid_merge_supports_device",
+    "gpc_hip_pyramid_merge_correspondences_device", "gpc_hip_pyramid_batch_device", "gpc_hip_pyramid_sequence_device",
+    "gpc_hip_pyramid_batch", "gpc_hip_pyramid_sequence",
 ]
 
 
@@ -228,6 +231,17 @@ def load():
                                               C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gpc_hip_refine_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_pyramid_levels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.gpc_hip_pyramid_down_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.gpc_hip_pyramid_merge_supports_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                        C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.gpc_hip_pyramid_merge_correspondences_device.argtypes = L.gpc_hip_pyramid_merge_supports_device.argtypes
+    L.gpc_hip_pyramid_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.POINTER(Settings), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_pyramid_batch.argtypes = L.gpc_hip_pyramid_batch_device.argtypes
+    L.gpc_hip_pyramid_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Settings),
+                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_pyramid_sequence.argtypes = L.gpc_hip_pyramid_sequence_device.argtypes
     L.gpc_hip_match_batch_device_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(Settings), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                     C.c_void_p]
@@ -326,6 +340,14 @@ POINTS_DTYPE = np.dtype([("rx", "<i4"), ("ry", "<i4"), ("px", "<i4"), ("py", "<i
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def pyramid_levels(width, height, levels):
+    """(status, widths, heights) of gpc_hip_pyramid_levels: the sizes of the levels of a width x height image, host only"""
+    n = max(int(levels), 1)
+    ws, hs = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    st = load().gpc_hip_pyramid_levels(int(width), int(height), int(levels), _ptr(ws), _ptr(hs))
+    return st, ws, hs
 
 
 def kept_count(pts, width, height):
@@ -976,6 +998,74 @@ class Context:
         self._ck(self.L.gpc_hip_refine_supports(self.h, _ptr(records), cap, _ptr(counts), _ptr(imgL), _ptr(imgR), W, H, P,
                                                 int(radius), _ptr(ref), _ptr(out)))
         return ref, out
+
+    # ---- matching over an image pyramid (gpc_hip_pyramid_*): per-level matches merged on the device
+    def pyramid_down_device(self, d_src, width, height, nimages, d_dst):
+        """One 2x2-mean step over [nimages][height][width] bytes in HBM -> [nimages][height // 2][width // 2]; asynchronous."""
+        self._ck(self.L.gpc_hip_pyramid_down_device(self.h, C.c_void_p(d_src), int(width), int(height), int(nimages),
+                                                    C.c_void_p(d_dst)))
+
+    def pyramid_merge_device(self, d_rec, caps, d_cnt, corr, width, height, npairs, d_out, cap_per_pair, d_counts,
+                             d_level_counts):
+        """The merge alone: d_rec[l], caps[l], d_cnt[l] are level l's unmapped records [npairs][caps[l]] (corr: CORR_DTYPE,
+        else SUPPORT_DTYPE) and counts [npairs] in HBM -> d_out[npairs][cap_per_pair] in level 0's coordinates, d_counts
+        [npairs], d_level_counts [levels][npairs]; asynchronous, no forest needed.  Pointers are integers."""
+        levels = len(d_rec)
+        if not (len(caps) == len(d_cnt) == levels):
+            raise ValueError("d_rec, caps, d_cnt: one entry per level")
+        recs = (C.c_void_p * levels)(*[C.c_void_p(int(p)) for p in d_rec])
+        cnts = (C.c_void_p * levels)(*[C.c_void_p(int(p)) for p in d_cnt])
+        cap_arr = (C.c_int32 * levels)(*[int(v) for v in caps])
+        fn = self.L.gpc_hip_pyramid_merge_correspondences_device if corr else self.L.gpc_hip_pyramid_merge_supports_device
+        self._ck(fn(self.h, C.cast(recs, C.c_void_p), C.cast(cap_arr, C.c_void_p), C.cast(cnts, C.c_void_p), int(width),
+                    int(height), int(npairs), levels, C.c_void_p(d_out), int(cap_per_pair), C.c_void_p(d_counts),
+                    C.c_void_p(d_level_counts)))
+
+    def pyramid_batch_device(self, d_rawL, d_rawR, width, height, npairs, levels, settings, d_out, cap_per_pair, d_counts,
+                             d_level_counts, d_ncand=0):
+        """match_batch_device on every level of the pairs' pyramids, merged: d_out[npairs][cap_per_pair] supports in level 0's
+        coordinates, d_counts[npairs], d_level_counts[levels][npairs], d_ncand[levels][npairs][2] (optional)."""
+        self._ck(self.L.gpc_hip_pyramid_batch_device(self.h, C.c_void_p(d_rawL), C.c_void_p(d_rawR), int(width), int(height),
+                                                     int(npairs), int(levels), C.byref(settings), C.c_void_p(d_out),
+                                                     int(cap_per_pair), C.c_void_p(d_counts), C.c_void_p(d_level_counts),
+                                                     C.c_void_p(d_ncand or 0)))
+
+    def pyramid_sequence_device(self, d_frames, width, height, nframes, levels, settings, d_out, cap_per_pair, d_counts,
+                                d_level_counts, d_ncand=0):
+        """match_sequence_device on every level, merged: d_out[nframes-1][cap_per_pair] correspondences, d_counts[nframes-1],
+        d_level_counts[levels][nframes-1], d_ncand[levels][nframes] (optional)."""
+        self._ck(self.L.gpc_hip_pyramid_sequence_device(self.h, C.c_void_p(d_frames), int(width), int(height), int(nframes),
+                                                        int(levels), C.byref(settings), C.c_void_p(d_out), int(cap_per_pair),
+                                                        C.c_void_p(d_counts), C.c_void_p(d_level_counts),
+                                                        C.c_void_p(d_ncand or 0)))
+
+    def pyramid_batch(self, rawL, rawR, levels, settings, cap, out=None):
+        """Host pairs [P, H, W] uint8 (pageable or page-locked) -> (supports [P, cap], counts [P], level_counts [levels, P],
+        ncand [levels, P, 2], status).  `out` is written only as far as each pair's records go."""
+        rawL, rawR = _host_frames(rawL), _host_frames(rawR)
+        if rawL.ndim != 3 or rawL.shape != rawR.shape:
+            raise ValueError("rawL, rawR: [P, H, W] of one shape")
+        P, H, W = rawL.shape
+        out = out if out is not None else np.zeros((P, cap), SUPPORT_DTYPE)
+        counts, lc, ncand = np.zeros(P, np.int32), np.zeros((levels, P), np.int32), np.zeros((levels, P, 2), np.int32)
+        st = self.L.gpc_hip_pyramid_batch(self.h, _ptr(rawL), _ptr(rawR), W, H, P, int(levels), C.byref(settings), _ptr(out),
+                                          int(cap), _ptr(counts), _ptr(lc), _ptr(ncand))
+        self._ck(st, allow=(E_CAPACITY,))
+        return out, counts, lc, ncand, st
+
+    def pyramid_sequence(self, frames, levels, settings, cap, out=None):
+        """Host frames [N, H, W] uint8 -> (correspondences [N-1, cap], counts [N-1], level_counts [levels, N-1], ncand
+        [levels, N], status)."""
+        frames = _host_frames(frames)
+        if frames.ndim != 3 or frames.shape[0] < 2:
+            raise ValueError("frames: [N, H, W], N >= 2")
+        N, H, W = frames.shape
+        out = out if out is not None else np.zeros((N - 1, cap), CORR_DTYPE)
+        counts, lc, ncand = np.zeros(N - 1, np.int32), np.zeros((levels, N - 1), np.int32), np.zeros((levels, N), np.int32)
+        st = self.L.gpc_hip_pyramid_sequence(self.h, _ptr(frames), W, H, N, int(levels), C.byref(settings), _ptr(out), int(cap),
+                                             _ptr(counts), _ptr(lc), _ptr(ncand))
+        self._ck(st, allow=(E_CAPACITY,))
+        return out, counts, lc, ncand, st
 
     # ---- fern training: the scoring loop
     def train_set(self, triplets):
