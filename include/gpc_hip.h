@@ -280,7 +280,8 @@ int gpc_hip_host_threads(const gpc_hip_ctx* ctx);
  * counts arrived), [2] the last chunk of packed records landed in host memory, [3] the expansion / delivery done (the
  * call returned).  All 0 for calls that took another path (one or two pairs written directly, the device-wide matchers). */
 int gpc_hip_batch_stages(const gpc_hip_ctx* ctx, float* ms4);
-/* The CPU each worker thread last ran a job on (returns the number of workers; fills at most cap entries). */
+/* The CPU each worker thread last ran a job on, or started on if it has run none yet (returns the number of workers;
+ * fills at most cap entries). */
 int gpc_hip_host_worker_cpus(gpc_hip_ctx* ctx, int* cpus, int cap);
 /* Batch calls of this context that ran their chunk pipeline on a thread bound to the GPU's NUMA node because the caller's
  * thread was on another socket (GPC_HIP_NO_FEEDER=1: never). */

@@ -273,6 +273,7 @@ def load():
     L.gpc_hip_extract_triplets.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
     L.gpc_hip_extract_triplets_device.argtypes = L.gpc_hip_extract_triplets.argtypes
     L.gpc_hip_train_set_read.argtypes = [vp, vp, ci, ci, vp]
+    L.gpc_hip_debug_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -284,6 +285,14 @@ def _check(L, ctx, status, allow=()):
     if status == E_HIP and ctx:
         msg += ": " + L.gpc_hip_last_error(ctx).decode()
     raise GpcError(status, msg)
+
+
+def live_resources():
+    """(device blocks, device bytes, page-locked blocks, streams + events) the library holds right now, over every context
+    of the process (gpc_hip_debug_live_resources); what callers own through pinned_empty is not counted"""
+    out = (C.c_uint64 * 4)()
+    _check(load(), None, load().gpc_hip_debug_live_resources(out))
+    return tuple(int(v) for v in out)
 
 
 def expand_packed(packed, rows, n):

@@ -11,6 +11,7 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cctype>
 #include <condition_variable>
 #include <cstdio>
@@ -19,6 +20,7 @@
 #include <ctime>
 #include <deque>
 #include <map>
+#include <memory>
 #include <utility>
 #include <mutex>
 #include <string>
@@ -44,6 +46,7 @@
 #include "k_track_stream.h"
 #include "k_train.h"
 #include "k_union.h"
+#include "owners.h"
 #include "pyramid_host.h"
 #include "track_stream_host.h"
 
@@ -97,13 +100,69 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_trs_fill", "k_trs_scatter", "k_trs_link", "k_trs_settle", "k_trs_scan", "k_trs_walk", "k_trs_save", "k_trs_ncand",
     "k_score_records", "k_score_matchable", "k_refine", "k_pyr_down", "k_pyr_keep", "k_pyr_scan", "k_pyr_write"};
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
+// The owners of owners.h over the HIP runtime.  Everything the library allocates passes through these four backends, which
+// also keep the process-wide counts that gpc_hip_debug_live_resources reports.
+std::atomic<uint64_t> g_live[4];  // device blocks, device bytes, page-locked blocks, streams + events
+struct DevMem {
+  using status = hipError_t;
+  static hipError_t alloc(void** p, size_t bytes, unsigned) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) ++g_live[0], g_live[1] += bytes;
+    return e;
+  }
+  static hipError_t release(void* p, size_t bytes) {
+    --g_live[0], g_live[1] -= bytes;
+    return hipFree(p);
+  }
 };
+struct PinnedMem {
+  using status = hipError_t;
+  static hipError_t alloc(void** p, size_t bytes, unsigned flags) {
+    const hipError_t e = hipHostMalloc(p, bytes, flags);
+    if (e == hipSuccess) ++g_live[2];
+    return e;
+  }
+  static hipError_t release(void* p, size_t) {
+    --g_live[2];
+    return hipHostFree(p);
+  }
+};
+struct StreamApi {
+  using handle = hipStream_t;
+  using status = hipError_t;
+  static hipError_t create(hipStream_t* s, unsigned flags) {
+    const hipError_t e = hipStreamCreateWithFlags(s, flags);
+    if (e == hipSuccess) ++g_live[3];
+    return e;
+  }
+  static hipError_t destroy(hipStream_t s) {
+    --g_live[3];
+    return hipStreamDestroy(s);
+  }
+};
+struct EventApi {
+  using handle = hipEvent_t;
+  using status = hipError_t;
+  static hipError_t create(hipEvent_t* ev, unsigned flags) {
+    const hipError_t e = hipEventCreateWithFlags(ev, flags);
+    if (e == hipSuccess) ++g_live[3];
+    return e;
+  }
+  static hipError_t destroy(hipEvent_t ev) {
+    --g_live[3];
+    return hipEventDestroy(ev);
+  }
+};
+template <class T>
+using DevBlock = gpc::Block<DevMem, T>;
+using DevBuf = DevBlock<void>;
+template <class T>
+using Pinned = gpc::Block<PinnedMem, T>;
+using Stream = gpc::Handle<StreamApi>;
+using Event = gpc::Handle<EventApi>;
 
 struct TimedSpan {
-  hipEvent_t a, b;
+  Event a, b;
   int kid;
 };
 
@@ -147,12 +206,17 @@ class ExpandPool {
     groups_.clear();
     if (bind && groups) groups_ = *groups;
     cpus_.assign((size_t)nthreads, -1);
+    started_ = 0;
     for (int i = 0; i < nthreads; ++i)
       threads_.emplace_back([this, i] {
         if (!groups_.empty()) (void)sched_setaffinity(0, sizeof(cpu_set_t), &groups_[(size_t)i % groups_.size()]);
         else if (have_bind_) (void)sched_setaffinity(0, sizeof bind_, &bind_);
         run(i);
       });
+    // every worker has reported the CPU it starts on: worker_cpus() has an entry for a worker that is never handed a job
+    // (with eight workers about one call in four of 32 pairs leaves one idle)
+    std::unique_lock<std::mutex> g(m_);
+    done_.wait(g, [&] { return started_ == nthreads; });
   }
   void stop() {
     {
@@ -179,7 +243,7 @@ class ExpandPool {
     for (int s = 0; s < 8; ++s) wait_slot(s);
   }
   int size() const { return (int)threads_.size(); }
-  // the CPU every worker last ran a job on (diagnostics: gpc_hip_host_worker_cpus)
+  // the CPU every worker started on or last ran a job on (diagnostics: gpc_hip_host_worker_cpus)
   int worker_cpus(int* out, int cap) {
     std::lock_guard<std::mutex> g(m_);
     int n = 0;
@@ -195,6 +259,7 @@ class ExpandPool {
   std::mutex m_;
   std::condition_variable cv_, done_;
   int pending_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int started_ = 0;
   bool quit_ = false;
   bool have_bind_ = false;
   cpu_set_t bind_;
@@ -203,23 +268,26 @@ class ExpandPool {
 
 }  // namespace
 
+// Who frees what: every block, stream and event below is an owner (owners.h) and goes when the context is deleted, in
+// reverse order of declaration -- no list to extend.  The order that matters is kept by gpc_hip_destroy and by where
+// own_stream stands: gpc_hip_destroy waits for `stream` and for every stream the context made before `delete` frees a
+// block; it stops the expansion pool, whose workers read and write the page-locked blocks, before `delete` frees those;
+// own_stream is the first owner declared, so it is destroyed last.
 struct gpc_hip_ctx {
   int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
+  Stream own_stream;
+  hipStream_t stream = nullptr;   // own_stream or the caller's (gpc_hip_set_stream): not owned
   // gpc_hip_match_batch: upload / download streams and the events that chain a chunk's stages
-  hipStream_t s_in = nullptr, s_out = nullptr, s_cnt = nullptr;
-  hipStream_t s_aux = nullptr;            // the non-epipolar matcher's launch for over-large partitions runs beside the main one
-  hipEvent_t e_fork = nullptr, e_join = nullptr;
-  hipEvent_t e_flag = nullptr;            // the device-wide matchers' plan words have arrived on the host
-  hipEvent_t e_in[4] = {}, e_comp[4] = {}, e_cnt[4] = {}, e_out[4] = {};
+  Stream s_in, s_out, s_cnt;
+  Stream s_aux;                   // the non-epipolar matcher's launch for over-large partitions runs beside the main one
+  Event e_fork, e_join;
+  Event e_flag;                   // the device-wide matchers' plan words have arrived on the host
+  Event e_in[4], e_comp[4], e_cnt[4], e_out[4];
   DevBuf packed;                  // packed results of the chunks in flight (3 slots)
-  void* h_stage = nullptr;        // page-locked landing area of packed results (4 slots)
-  size_t h_stage_cap = 0;
-  void* h_in = nullptr;           // page-locked bounce buffer for PAGEABLE input images (2 slots x 2 sides x a chunk)
-  size_t h_in_cap = 0;
-  int32_t* h_cnt = nullptr;       // page-locked landing area of counts [npairs] + candidate counts [npairs][2]: a copy to the
-  size_t h_cnt_cap = 0;           // caller's (pageable) arrays would block the host until the chunk's kernels are done (bytes)
+  Pinned<void> h_stage;           // page-locked landing area of packed results (4 slots)
+  Pinned<void> h_in;              // page-locked bounce buffer for PAGEABLE input images (2 slots x 2 sides x a chunk)
+  Pinned<int32_t> h_cnt;          // page-locked landing area of counts [npairs] + candidate counts [npairs][2]: a copy to the
+                                  // caller's (pageable) arrays would block the host until the chunk's kernels are done
   ExpandPool pool;
   // host clock at the stages of the last gpc_hip_match_batch / _packed call, ms since its entry (gpc_hip_batch_stages):
   // [0] last upload seen complete, [1] last chunk's kernels done (its counts have arrived), [2] last chunk of packed
@@ -239,8 +307,8 @@ struct gpc_hip_ctx {
   // join (which then takes one workgroup per CU less: a wave slot per SIMD stays free for them).  A lane is SWAPPED INTO
   // the members below for the duration of a call (LaneScope), so every run_* function works on it unchanged.
   struct Lane {
-    hipStream_t s = nullptr;
-    hipEvent_t e_in = nullptr, e_hash = nullptr, e_join = nullptr;
+    Stream s;
+    Event e_in, e_hash, e_join;
     DevBuf smooth, grad, codes, stats, jstate, staged, rowcnt;
     size_t jstate_granules = 0;
     uint32_t join_epoch = 0;
@@ -277,7 +345,7 @@ struct gpc_hip_ctx {
   // the host forms of scoring, tracks and filtering (Stage): what a call or a chunk of it sends up and brings down; the
   // copies that read a piece of the transfer arena are done
   DevBuf stage;
-  hipEvent_t e_stage[2] = {};
+  Event e_stage[2];
   // point tracks (gpc_hip_track_*): per-pixel planes of pairs 1 .. P-1, predecessor per record, head counts per chunk
   DevBuf tr_plane, tr_pred, tr_blk;
   // match filtering (gpc_hip_consensus_*): class and record index per sorted position, cursors and first positions per pair
@@ -293,7 +361,7 @@ struct gpc_hip_ctx {
   DevBuf gkv;  // records (code, pixel index) of the partitioned device-wide matchers, by bin
   DevBuf gkeys[2], gvals[2], ghist, gmisc, hkeys[2], hvals[2], hrec;
   DevBuf gpart;       // partition plan of the non-epipolar matcher (k_partition.h) + one overflow word for the batch
-  int32_t* h_flag = nullptr;  // page-locked landing word of that overflow flag
+  Pinned<int32_t> h_flag;     // page-locked landing word of that overflow flag
   int no_partition = 0;       // GPC_HIP_NO_PARTITION: always take the radix-sort path (A/B checks)
   int rows_per_chunk = 16;    // GPC_HIP_ROWS_PER_CHUNK: rows one partition workgroup scatters (A/B checks)
   int gp_log2bins = 0;        // GPC_HIP_GP_LOG2BINS = 8 .. 11: force the number of code-range bins (A/B checks)
@@ -311,8 +379,8 @@ struct gpc_hip_ctx {
   DevBuf jstate;
   size_t jstate_granules = 0;
   uint32_t join_epoch = 0;
-  int32_t* h_err = nullptr;   // page-locked, device-visible: a look-back of the fused join timed out
-  int32_t* d_err = nullptr;   // the device's address of that word
+  Pinned<int32_t> h_err;      // page-locked, device-visible: a look-back of the fused join timed out
+  int32_t* d_err = nullptr;   // the device's address of that word (a view of h_err)
   int no_fuse = 0;            // GPC_HIP_NO_FUSE: join + k_gather_rows as two launches (A/B checks)
   int fuse_always = 0;        // GPC_HIP_FUSE_ALWAYS: the fused join wherever it is possible, however small the launch (tests, A/B checks)
   int fuse_wgs = 0;           // GPC_HIP_FUSE_WGS: workgroups of the persistent join (tuning; default = what the device holds)
@@ -367,14 +435,12 @@ struct gpc_hip_ctx {
   // caller later frees the array the driver must suspend and restore the process's queues to drop it -- the next
   // submission then waits ~27 ms (measured: profiles/r05_a_cold_start.txt).  So pageable memory is copied by CPU threads
   // into / out of this arena, and the device reads / writes the arena over the link.
-  uint8_t* h_xfer = nullptr;
-  size_t h_xfer_cap = 0;
+  Pinned<uint8_t> h_xfer;
   // page-locked staging of gpc_hip_preprocess_begin / _fetch: [raw | smooth | grad | mask | count]
-  uint8_t* h_pre = nullptr;
-  size_t h_pre_cap = 0;
+  Pinned<uint8_t> h_pre;
   int pre_slot = -1, pre_W = 0, pre_H = 0;  // what _begin left for _fetch
   bool pre_have_mask = false;
-  hipEvent_t e_pre = nullptr;   // smooth and grad of that image have landed in the staging block
+  Event e_pre;                  // smooth and grad of that image have landed in the staging block
   // what gpc_hip_*_match_begin left for gpc_hip_match_fetch: results in the transfer arena (or, `direct`, already in the
   // caller's page-locked array), the count and the candidate counts in h_cnt[0 .. 2]
   struct PendingMatch {
@@ -393,11 +459,10 @@ struct gpc_hip_train_set {
   gpc_hip_ctx* owner = nullptr;
   int n = 0;
   long np = 0;                // n rounded up to a multiple of 256
-  uint8_t* planes = nullptr;  // [3][729][np]
-  uint8_t* flags = nullptr;   // [np]
-  int32_t* counts = nullptr;  // scratch: tp/fp per (candidate, tau) + tot
-  gpc::GpcSplit* d_cand = nullptr;
-  size_t counts_cap = 0, cand_cap = 0;
+  DevBlock<uint8_t> planes;   // [3][729][np]
+  DevBlock<uint8_t> flags;    // [np]
+  DevBlock<int32_t> counts;   // scratch: tp/fp per (candidate, tau) + tot
+  DevBlock<gpc::GpcSplit> d_cand;
   std::vector<int32_t> h_counts;  // host staging of the counters
 };
 
@@ -429,25 +494,21 @@ double host_ms() {
   return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
 }
 
-int ensure(gpc_hip_ctx* c, DevBuf& b, size_t bytes) {
+template <class T>
+int ensure(gpc_hip_ctx* c, DevBlock<T>& b, size_t bytes) {
   if (bytes <= b.cap) return GPC_OK;
-  if (b.p) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-  }
+  if (b.p) HIPCHK(c, hipStreamSynchronize(c->stream));
   // slack: growth without reallocation, and the fused join reads whole pixel-slot rows (up to 16 KiB past a row's end)
-  size_t want = bytes + bytes / 8 + 65536;
-  HIPCHK(c, hipMalloc(&b.p, want));
-  b.cap = want;
+  HIPCHK(c, b.alloc(bytes + bytes / 8 + 65536));
   return GPC_OK;
 }
 
-void release(DevBuf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
+// a page-locked block of exactly `want` bytes in place of the old one.  Waits for nothing: the caller does where the device
+// may still use the old block, and decides when to grow and by how much.
+template <class T>
+int ensure_pinned(gpc_hip_ctx* c, Pinned<T>& b, size_t want) {
+  HIPCHK(c, b.alloc(want, hipHostMallocDefault));
+  return GPC_OK;
 }
 
 struct Timed {
@@ -458,10 +519,10 @@ struct Timed {
   Timed(gpc_hip_ctx* ctx, int kid) : c(ctx), on(ctx->timing && (kid >= 32 || ((ctx->timing_mask >> kid) & 1u))) {
     if (!on) return;
     if (!c->free_spans.empty()) {
-      s = c->free_spans.back();
+      s = std::move(c->free_spans.back());
       c->free_spans.pop_back();
     } else {
-      if (hipEventCreate(&s.a) != hipSuccess || hipEventCreate(&s.b) != hipSuccess) {
+      if (s.a.create(hipEventDefault) != hipSuccess || s.b.create(hipEventDefault) != hipSuccess) {
         on = false;
         return;
       }
@@ -472,7 +533,7 @@ struct Timed {
   ~Timed() {
     if (!on) return;
     (void)hipEventRecord(s.b, c->stream);
-    c->spans.push_back(s);
+    c->spans.push_back(std::move(s));
   }
 };
 
@@ -666,6 +727,12 @@ void expand_rows(const uint32_t* packed, const int32_t* rows, int y0, int y1, lo
 }
 
 void ExpandPool::run(int index) {
+  {
+    std::lock_guard<std::mutex> g(m_);
+    cpus_[(size_t)index] = sched_getcpu();
+    ++started_;
+  }
+  done_.notify_all();
   for (;;) {
     ExpandJob j;
     {
@@ -960,14 +1027,14 @@ JoinPlan plan_join(const gpc_hip_ctx* c, int W) {
 // gpc_hip_destroy, and says WHICH launch failed.
 int check_join_err(gpc_hip_ctx* c) {
 #ifdef RJ_DBG_COUNT
-  if (c->h_err && c->h_err[1]) {
-    fprintf(stderr, "[RJ_DBG_COUNT] look-backs %d, windows with a row that had not published %d, displaced keys that met their copy %d\n", c->h_err[1], c->h_err[2], c->h_err[3]);
-    c->h_err[1] = c->h_err[2] = c->h_err[3] = 0;
+  if (c->h_err.p && c->h_err.p[1]) {
+    fprintf(stderr, "[RJ_DBG_COUNT] look-backs %d, windows with a row that had not published %d, displaced keys that met their copy %d\n", c->h_err.p[1], c->h_err.p[2], c->h_err.p[3]);
+    c->h_err.p[1] = c->h_err.p[2] = c->h_err.p[3] = 0;
   }
 #endif
-  if (c->h_err) {
+  if (c->h_err.p) {
     // (one exchange: a launch still in flight may store its epoch between a load and a clearing store, and would be lost)
-    const int32_t ep = __atomic_exchange_n(c->h_err, 0, __ATOMIC_ACQ_REL);
+    const int32_t ep = __atomic_exchange_n(c->h_err.p, 0, __ATOMIC_ACQ_REL);
     if (ep) {
       snprintf(c->err, sizeof(c->err), "k_row_join_fused: a row waited too long for the rows before it in fused launch %d of this "
                "context (%u launched so far): THAT launch's supports are not to be used; a call that reports this at its start "
@@ -994,10 +1061,10 @@ int join_shards(const gpc_hip_ctx* c, int npairs) {
 // consistent by the kernel itself (the last draw resets a counter; granules carry the launch's epoch).
 int ensure_join_state(gpc_hip_ctx* c, size_t granules) {
   const size_t tk_bytes = sizeof(uint32_t) * RJ_SHARDS * RJ_TICKET_STRIDE;
-  if (!c->h_err) {
-    HIPCHK(c, hipHostMalloc((void**)&c->h_err, 64, hipHostMallocMapped));
-    memset(c->h_err, 0, 64);
-    HIPCHK(c, hipHostGetDevicePointer((void**)&c->d_err, c->h_err, 0));
+  if (!c->h_err.p) {
+    HIPCHK(c, c->h_err.alloc(64, hipHostMallocMapped));
+    memset(c->h_err.p, 0, 64);
+    HIPCHK(c, hipHostGetDevicePointer((void**)&c->d_err, c->h_err.p, 0));
   }
   if (granules > c->jstate_granules || c->join_epoch >= (1u << 30) - 2u) {
     CHK(ensure(c, c->jstate, tk_bytes + sizeof(unsigned long long) * granules));
@@ -1009,16 +1076,16 @@ int ensure_join_state(gpc_hip_ctx* c, size_t granules) {
 }
 
 int ensure_flag_event(gpc_hip_ctx* c) {
-  if (!c->e_flag) HIPCHK(c, hipEventCreateWithFlags(&c->e_flag, hipEventDisableTiming));
+  if (!c->e_flag) HIPCHK(c, c->e_flag.create(hipEventDisableTiming));
   return GPC_OK;
 }
 
 // The second stream of the device-wide matchers: a launch for the few over-large partitions / bins runs beside the main one.
 int ensure_aux_stream(gpc_hip_ctx* c) {
   if (c->s_aux) return GPC_OK;
-  HIPCHK(c, hipStreamCreateWithFlags(&c->s_aux, hipStreamNonBlocking));
-  HIPCHK(c, hipEventCreateWithFlags(&c->e_fork, hipEventDisableTiming));
-  HIPCHK(c, hipEventCreateWithFlags(&c->e_join, hipEventDisableTiming));
+  HIPCHK(c, c->s_aux.create(hipStreamNonBlocking));
+  HIPCHK(c, c->e_fork.create(hipEventDisableTiming));
+  HIPCHK(c, c->e_join.create(hipEventDisableTiming));
   return GPC_OK;
 }
 
@@ -1284,7 +1351,7 @@ template <class Words>
 Words plan_words(const gpc_hip_ctx* c) {
   static_assert(sizeof(Words) == 4 * sizeof(int32_t), "a planner leaves four words");
   Words w;
-  memcpy(&w, c->h_flag, sizeof w);
+  memcpy(&w, c->h_flag.p, sizeof w);
   return w;
 }
 
@@ -1300,7 +1367,7 @@ int partition_io(gpc_hip_ctx* c, const GlobalPlan& g, int H, int npairs, const u
   L.nchunk = (rows + L.rows_per_chunk - 1) / L.rows_per_chunk;
   CHK(ensure(c, c->staged, sizeof(uint2) * (size_t)(g.nmax / 2) * npairs));  // (left, right) position per match
   CHK(ensure(c, c->gkv, sizeof(uint2) * (size_t)g.bs.recs * npairs));
-  if (!c->h_flag) HIPCHK(c, hipHostMalloc((void**)&c->h_flag, 64, hipHostMallocDefault));
+  if (!c->h_flag.p) CHK(ensure_pinned(c, c->h_flag, 64));
   CHK(ensure_flag_event(c));
   io.codes = (const uint32_t*)c->codes.p;
   io.wcand = wide_codes(c) ? d_cand : nullptr;
@@ -1342,7 +1409,7 @@ int partition_round(gpc_hip_ctx* c, const GlobalPlan& g, int W, int H, int npair
     CHK(launch_planner());
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipMemcpyAsync(c->h_flag, d_flag, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_flag.p, d_flag, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipEventRecord(c->e_flag, c->stream));
   {
     Timed t(c, KID_GLOBAL_SORT);
@@ -1859,28 +1926,18 @@ void host_copy_wait(gpc_hip_ctx* c) {
 
 // at least `bytes` of transfer arena; *dev receives the device's view of it
 int xfer_reserve(gpc_hip_ctx* c, size_t bytes, uint8_t** dev) {
-  if (bytes > c->h_xfer_cap) {
+  if (bytes > c->h_xfer.cap) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->h_xfer) HIPCHK(c, hipHostFree(c->h_xfer));
-    c->h_xfer = nullptr;
-    c->h_xfer_cap = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    HIPCHK(c, hipHostMalloc((void**)&c->h_xfer, want, hipHostMallocDefault));
-    c->h_xfer_cap = want;
+    CHK(ensure_pinned(c, c->h_xfer, bytes + bytes / 4 + 4096));
   }
-  HIPCHK(c, hipHostGetDevicePointer((void**)dev, c->h_xfer, 0));
+  HIPCHK(c, hipHostGetDevicePointer((void**)dev, c->h_xfer.p, 0));
   return GPC_OK;
 }
 
 // at least `bytes` of the page-locked landing area of small per-pair words
 int pinned_area(gpc_hip_ctx* c, size_t bytes) {
-  if (bytes <= c->h_cnt_cap) return GPC_OK;
-  if (c->h_cnt) HIPCHK(c, hipHostFree(c->h_cnt));
-  c->h_cnt = nullptr;
-  c->h_cnt_cap = 0;
-  HIPCHK(c, hipHostMalloc((void**)&c->h_cnt, bytes, hipHostMallocDefault));
-  c->h_cnt_cap = bytes;
-  return GPC_OK;
+  if (bytes <= c->h_cnt.cap) return GPC_OK;
+  return ensure_pinned(c, c->h_cnt, bytes);
 }
 // ... for npairs counts + 2 * npairs candidate counts
 int pinned_counts(gpc_hip_ctx* c, int npairs) { return pinned_area(c, sizeof(int32_t) * 3 * (size_t)npairs); }
@@ -1954,10 +2011,10 @@ struct LaneScope {
 int ensure_lanes(gpc_hip_ctx* c) {
   for (auto& l : c->lanes) {
     if (l.s) continue;
-    HIPCHK(c, hipStreamCreateWithFlags(&l.s, hipStreamNonBlocking));
-    HIPCHK(c, hipEventCreateWithFlags(&l.e_in, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&l.e_hash, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&l.e_join, hipEventDisableTiming));
+    HIPCHK(c, l.s.create(hipStreamNonBlocking));
+    HIPCHK(c, l.e_in.create(hipEventDisableTiming));
+    HIPCHK(c, l.e_hash.create(hipEventDisableTiming));
+    HIPCHK(c, l.e_join.create(hipEventDisableTiming));
   }
   return GPC_OK;
 }
@@ -2132,7 +2189,7 @@ int gpc_hip_create(int device, gpc_hip_ctx** out) {
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return GPC_E_NO_DEVICE;
   gpc_hip_ctx* c = new gpc_hip_ctx();
   c->device = device;
-  if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
+  if (c->own_stream.create(hipStreamNonBlocking) != hipSuccess) {
     delete c;
     return GPC_E_NO_DEVICE;
   }
@@ -2229,62 +2286,14 @@ int gpc_hip_destroy(gpc_hip_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)drain_lanes(c);
   (void)hipStreamSynchronize(c->stream);
+  for (hipStream_t s : {c->own_stream.h, c->s_in.h, c->s_out.h, c->s_cnt.h, c->s_aux.h})
+    if (s) (void)hipStreamSynchronize(s);
   // a fused-join time-out nobody has asked about (callers that only ever waited on their own stream): say so, once
   const int pending_err = check_join_err(c);
   if (pending_err != GPC_OK) fprintf(stderr, "gpc_hip_destroy: %s\n", c->err);
-  DevBuf* bufs[] = {&c->raw, &c->smooth, &c->grad, &c->candmap, &c->codes, &c->staged, &c->rowcnt,
-                    &c->stats, &c->out, &c->counts, &c->ncand, &c->mask, &c->gkeys[0], &c->gkeys[1],
-                    &c->gvals[0], &c->gvals[1], &c->ghist, &c->gmisc, &c->hkeys[0], &c->hkeys[1],
-                    &c->hvals[0], &c->hvals[1], &c->hrec, &c->forest_dev, &c->packed, &c->gpart, &c->jstate, &c->gkv,
-                    &c->res_smooth, &c->res_grad, &c->ext_raw, &c->ext_smooth, &c->ext_grad, &c->ext_groups,
-                    &c->sstats, &c->all_rec, &c->all_cnt, &c->stage, &c->tr_plane, &c->tr_pred, &c->tr_blk,
-                    &c->cs_key, &c->cs_idx, &c->cs_cur, &c->cs_start, &c->cs_blk, &c->cs_keep,
-                    &c->py_img, &c->py_rec, &c->py_cnt, &c->py_plane, &c->py_flags, &c->py_blk};
   while (!c->train_sets.empty()) (void)gpc_hip_train_set_destroy(c, c->train_sets.back());
   while (!c->track_streams.empty()) (void)gpc_hip_track_stream_destroy(c, c->track_streams.back());
-  for (DevBuf* b : bufs) release(*b);
-  for (auto& s : c->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
-  for (auto& s : c->free_spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
-  if (c->s_in) {
-    (void)hipStreamDestroy(c->s_in);
-    (void)hipStreamDestroy(c->s_out);
-    (void)hipStreamDestroy(c->s_cnt);
-    for (int i = 0; i < 4; ++i) {
-      (void)hipEventDestroy(c->e_in[i]);
-      (void)hipEventDestroy(c->e_comp[i]);
-      (void)hipEventDestroy(c->e_cnt[i]);
-      (void)hipEventDestroy(c->e_out[i]);
-    }
-  }
-  if (c->e_flag) (void)hipEventDestroy(c->e_flag);
-  if (c->e_pre) (void)hipEventDestroy(c->e_pre);
-  for (hipEvent_t e : c->e_stage)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& l : c->lanes) {
-    if (l.s) {
-      (void)hipStreamSynchronize(l.s);
-      (void)hipStreamDestroy(l.s);
-      (void)hipEventDestroy(l.e_in);
-      (void)hipEventDestroy(l.e_hash);
-      (void)hipEventDestroy(l.e_join);
-    }
-    DevBuf* lb[] = {&l.smooth, &l.grad, &l.codes, &l.stats, &l.jstate, &l.staged, &l.rowcnt};
-    for (DevBuf* b : lb) release(*b);
-  }
-  if (c->s_aux) {
-    (void)hipStreamDestroy(c->s_aux);
-    (void)hipEventDestroy(c->e_fork);
-    (void)hipEventDestroy(c->e_join);
-  }
   c->pool.stop();
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  if (c->h_in) (void)hipHostFree(c->h_in);
-  if (c->h_cnt) (void)hipHostFree(c->h_cnt);
-  if (c->h_pre) (void)hipHostFree(c->h_pre);
-  if (c->h_xfer) (void)hipHostFree(c->h_xfer);
-  if (c->h_flag) (void)hipHostFree(c->h_flag);
-  if (c->h_err) (void)hipHostFree(c->h_err);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   return pending_err;
 }
@@ -2620,20 +2629,16 @@ static int preprocess_begin(gpc_hip_ctx* c, const uint8_t* raw, int W, int H, in
     CHK(ensure(c, c->res_grad, 2 * n));
     c->res_n = n;
   }
-  if (!c->e_pre) HIPCHK(c, hipEventCreateWithFlags(&c->e_pre, hipEventDisableTiming));
+  if (!c->e_pre) HIPCHK(c, c->e_pre.create(hipEventDisableTiming));
   // staging: raw | smooth | grad | mask (every candidate a pixel can be) | count   (all offsets multiples of 16)
   const size_t mask_bytes = pad16(sizeof(int32_t) * maxcand);
   const size_t need = 3 * n + mask_bytes + 64;
-  if (need > c->h_pre_cap) {
+  if (need > c->h_pre.cap) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->h_pre) HIPCHK(c, hipHostFree(c->h_pre));
-    c->h_pre = nullptr;
-    c->h_pre_cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&c->h_pre, need + need / 8, hipHostMallocDefault));
-    c->h_pre_cap = need + need / 8;
+    CHK(ensure_pinned(c, c->h_pre, need + need / 8));
   }
   uint8_t* d_stage = nullptr;  // the device's view of the staging block
-  HIPCHK(c, hipHostGetDevicePointer((void**)&d_stage, c->h_pre, 0));
+  HIPCHK(c, hipHostGetDevicePointer((void**)&d_stage, c->h_pre.p, 0));
   const int slot = c->res_next;
   {
     std::lock_guard<std::mutex> g(g_res_mu);
@@ -2646,7 +2651,7 @@ static int preprocess_begin(gpc_hip_ctx* c, const uint8_t* raw, int W, int H, in
   // the image: a page-locked one is read where it lies, a pageable one (ndb::Buffer, std::vector) passes through staging
   const uint8_t* v_raw = static_cast<const uint8_t*>(device_view_of_host(raw));
   if (!v_raw || ((uintptr_t)v_raw & 15u)) {
-    memcpy(c->h_pre, raw, n);
+    memcpy(c->h_pre.p, raw, n);
     v_raw = d_stage;
   }
   CHK(dev_copy16(c, c->raw.p, v_raw, n));
@@ -2680,7 +2685,7 @@ static int preprocess_fetch(gpc_hip_ctx* c, uint8_t* smooth, uint8_t* grad, int3
   const size_t n = (size_t)W * H;
   const size_t maxcand = (size_t)(W - 2 * GPC_R) * (H - 2 * GPC_R);
   const size_t mask_bytes = pad16(sizeof(int32_t) * maxcand);
-  const uint8_t* h_smooth = c->h_pre + n;
+  const uint8_t* h_smooth = c->h_pre.p + n;
   const uint8_t* h_grad = h_smooth + n;
   const int32_t* h_mask = reinterpret_cast<const int32_t*>(h_grad + n);
   const int32_t* h_count = reinterpret_cast<const int32_t*>(h_grad + n + mask_bytes);
@@ -2754,8 +2759,8 @@ int gpc_hip_hash_codes(gpc_hip_ctx* c, const uint8_t* smooth, const uint8_t* gra
   uint8_t* d_arena = nullptr;
   CHK(xfer_reserve(c, 4 * n, &d_arena));
   CHK(ensure_pool(c));
-  host_copy(c, c->h_xfer, smooth, n, true);
-  host_copy(c, c->h_xfer + n, grad, n, true);
+  host_copy(c, c->h_xfer.p, smooth, n, true);
+  host_copy(c, c->h_xfer.p + n, grad, n, true);
   host_copy_wait(c);
   CHK(dev_copy16(c, c->smooth.p, d_arena, n));
   c->grad_is_bits = false;  // the caller's byte image
@@ -2766,7 +2771,7 @@ int gpc_hip_hash_codes(gpc_hip_ctx* c, const uint8_t* smooth, const uint8_t* gra
                (uint32_t*)c->codes.p));
   CHK(dev_copy16(c, d_arena, c->codes.p, sizeof(uint32_t) * n));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  host_copy(c, codes, c->h_xfer, sizeof(uint32_t) * n, true);
+  host_copy(c, codes, c->h_xfer.p, sizeof(uint32_t) * n, true);
   host_copy_wait(c);
   return GPC_OK;
 }
@@ -2784,8 +2789,8 @@ int gpc_hip_hash_codes_groups(gpc_hip_ctx* c, const uint8_t* smooth, const uint8
   uint8_t* d_arena = nullptr;
   CHK(xfer_reserve(c, sizeof(uint32_t) * n * G, &d_arena));
   CHK(ensure_pool(c));
-  host_copy(c, c->h_xfer, smooth, n, true);
-  host_copy(c, c->h_xfer + n, grad, n, true);
+  host_copy(c, c->h_xfer.p, smooth, n, true);
+  host_copy(c, c->h_xfer.p + n, grad, n, true);
   host_copy_wait(c);
   CHK(dev_copy16(c, c->smooth.p, d_arena, n));
   c->grad_is_bits = false;
@@ -2795,7 +2800,7 @@ int gpc_hip_hash_codes_groups(gpc_hip_ctx* c, const uint8_t* smooth, const uint8
                G > 1 ? G : 0, 1));
   CHK(dev_copy16(c, d_arena, c->gdense.p, sizeof(uint32_t) * n * G));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  host_copy(c, codes, c->h_xfer, sizeof(uint32_t) * n * G, true);
+  host_copy(c, codes, c->h_xfer.p, sizeof(uint32_t) * n * G, true);
   host_copy_wait(c);
   return GPC_OK;
 }
@@ -2821,7 +2826,7 @@ static int match_preprocessed_begin(gpc_hip_ctx* c, const uint8_t* smoothL, cons
   CHK(ensure(c, c->stats, sizeof(int32_t) * GPC_STAT_STRIDE * 2));
   CHK(pinned_counts(c, 1));
   int32_t* d_cnt = nullptr;
-  HIPCHK(c, hipHostGetDevicePointer((void**)&d_cnt, c->h_cnt, 0));
+  HIPCHK(c, hipHostGetDevicePointer((void**)&d_cnt, c->h_cnt.p, 0));
   // Supports of the epipolar sort-matcher cross the link PACKED (x | xR << 16 + the row counts: 4 bytes instead of 12 -- a
   // 1024x436 pair's 3.2 MB of records were 60 us of the link, a third of the call) and are expanded into the caller's
   // array by the worker threads, who read 1.1 MB where they copied 3.2
@@ -2873,7 +2878,7 @@ static int match_preprocessed_begin(gpc_hip_ctx* c, const uint8_t* smoothL, cons
     CHK(ensure(c, c->smooth, 2 * n));
     CHK(ensure(c, c->grad, 2 * n));
     CHK(ensure(c, c->candmap, 2 * n));
-    uint8_t* h_in = c->h_xfer + in_off;
+    uint8_t* h_in = c->h_xfer.p + in_off;
     const bool par = in_bytes >= 512 * 1024;
     if (par) CHK(ensure_pool(c));
     host_copy(c, h_in, smoothL, n, par);
@@ -2935,11 +2940,11 @@ static int match_fetch(gpc_hip_ctx* c, void* out, int cap, int* n_out, int* ncl,
   if (!c || !c->pend.active || !n_out || cap < 0 || (cap > 0 && !out)) return GPC_E_INVALID;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   CHK(check_join_err(c));
-  const int32_t cnt = c->h_cnt[0];
+  const int32_t cnt = c->h_cnt.p[0];
   *n_out = cnt;
   if (c->pend.have_ncand) {
-    if (ncl) *ncl = c->h_cnt[1];
-    if (ncr) *ncr = c->h_cnt[2];
+    if (ncl) *ncl = c->h_cnt.p[1];
+    if (ncr) *ncr = c->h_cnt.p[2];
   }
   int ncopy = cnt < cap ? cnt : cap;
   if (ncopy > c->pend.cap_dev) ncopy = c->pend.cap_dev;
@@ -2948,16 +2953,16 @@ static int match_fetch(gpc_hip_ctx* c, void* out, int cap, int* n_out, int* ncl,
     const size_t bytes = c->pend.esz * (size_t)ncopy;
     uint8_t* d_arena = nullptr;
     CHK(xfer_reserve(c, bytes, &d_arena));
-    HIPCHK(c, hipMemcpyAsync(c->h_xfer, c->pend.dev_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_xfer.p, c->pend.dev_out, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const bool par = bytes >= 256 * 1024;
     if (par) CHK(ensure_pool(c));
-    host_copy(c, out, c->h_xfer, bytes, par);
+    host_copy(c, out, c->h_xfer.p, bytes, par);
     if (par) host_copy_wait(c);
   } else if (c->pend.packed && ncopy > 0) {
     const int H = c->pend.H;
-    const int32_t* rows = reinterpret_cast<const int32_t*>(c->h_xfer);
-    const uint32_t* words = reinterpret_cast<const uint32_t*>(c->h_xfer + pad16(sizeof(int32_t) * (size_t)H));
+    const int32_t* rows = reinterpret_cast<const int32_t*>(c->h_xfer.p);
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(c->h_xfer.p + pad16(sizeof(int32_t) * (size_t)H));
     const bool par = ncopy >= 32 * 1024;
     if (par) CHK(ensure_pool(c));
     const int parts = par ? (c->pool.size() > 1 ? c->pool.size() : 1) : 1;
@@ -2975,7 +2980,7 @@ static int match_fetch(gpc_hip_ctx* c, void* out, int cap, int* n_out, int* ncl,
     const size_t bytes = c->pend.esz * (size_t)ncopy;
     const bool par = bytes >= 256 * 1024;
     if (par) CHK(ensure_pool(c));
-    host_copy(c, out, c->h_xfer, bytes, par);
+    host_copy(c, out, c->h_xfer.p, bytes, par);
     if (par) host_copy_wait(c);
   }
   return (cnt > cap || cnt > c->pend.cap_dev) ? GPC_E_CAPACITY : GPC_OK;
@@ -3109,14 +3114,14 @@ int gpc_hip_debug_pipeline_events(gpc_hip_ctx* c, void* wait_before_preprocess, 
 
 static int batch_streams(gpc_hip_ctx* c) {
   if (c->s_in) return GPC_OK;
-  HIPCHK(c, hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking));
-  HIPCHK(c, hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking));
-  HIPCHK(c, hipStreamCreateWithFlags(&c->s_cnt, hipStreamNonBlocking));  // the counts: never queued behind bulk copies
+  HIPCHK(c, c->s_in.create(hipStreamNonBlocking));
+  HIPCHK(c, c->s_out.create(hipStreamNonBlocking));
+  HIPCHK(c, c->s_cnt.create(hipStreamNonBlocking));  // the counts: never queued behind bulk copies
   for (int i = 0; i < 4; ++i) {
-    HIPCHK(c, hipEventCreateWithFlags(&c->e_in[i], hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->e_comp[i], hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->e_cnt[i], hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->e_out[i], hipEventDisableTiming));
+    HIPCHK(c, c->e_in[i].create(hipEventDisableTiming));
+    HIPCHK(c, c->e_comp[i].create(hipEventDisableTiming));
+    HIPCHK(c, c->e_cnt[i].create(hipEventDisableTiming));
+    HIPCHK(c, c->e_out[i].create(hipEventDisableTiming));
   }
   return GPC_OK;
 }
@@ -3149,27 +3154,19 @@ static int match_batch_unpacked(gpc_hip_ctx* c, const uint8_t* rawL, const uint8
   if (bounce || land) CHK(ensure_pool(c));
   if (bounce) {
     const size_t need = 2 * 2 * n * (size_t)chunk;
-    if (need > c->h_in_cap) {
+    if (need > c->h_in.cap) {
       HIPCHK(c, hipStreamSynchronize(c->s_in));
-      if (c->h_in) HIPCHK(c, hipHostFree(c->h_in));
-      c->h_in = nullptr;
-      c->h_in_cap = 0;
-      HIPCHK(c, hipHostMalloc(&c->h_in, need, hipHostMallocDefault));
-      c->h_in_cap = need;
+      CHK(ensure_pinned(c, c->h_in, need));
     }
   }
   const size_t slot_bytes = sizeof(gpc_support) * (size_t)cap * chunk;
-  if (land && 2 * slot_bytes > c->h_stage_cap) {
+  if (land && 2 * slot_bytes > c->h_stage.cap) {
     c->pool.wait_all();
     HIPCHK(c, hipStreamSynchronize(c->s_out));
-    if (c->h_stage) HIPCHK(c, hipHostFree(c->h_stage));
-    c->h_stage = nullptr;
-    c->h_stage_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->h_stage, 2 * slot_bytes, hipHostMallocDefault));
-    c->h_stage_cap = 2 * slot_bytes;
+    CHK(ensure_pinned(c, c->h_stage, 2 * slot_bytes));
   }
-  int32_t* hc = c->h_cnt;
-  int32_t* hn = c->h_cnt + npairs;
+  int32_t* hc = c->h_cnt.p;
+  int32_t* hn = c->h_cnt.p + npairs;
   int status = GPC_OK;
   // fetch the supports of chunk k (its counts are on their way: wait for them, then one copy per pair)
   auto collect = [&](int k) -> int {
@@ -3178,7 +3175,7 @@ static int match_batch_unpacked(gpc_hip_ctx* c, const uint8_t* rawL, const uint8
     memcpy(counts + p0, hc + p0, sizeof(int32_t) * pc);
     if (ncand) memcpy(ncand + 2 * p0, hn + 2 * p0, sizeof(int32_t) * 2 * pc);
     if (land) c->pool.wait_slot(k & 1);  // the copies of chunk k-2 have left this landing slot
-    gpc_support* lslot = land ? reinterpret_cast<gpc_support*>((uint8_t*)c->h_stage + (size_t)(k & 1) * slot_bytes) : nullptr;
+    gpc_support* lslot = land ? reinterpret_cast<gpc_support*>((uint8_t*)c->h_stage.p + (size_t)(k & 1) * slot_bytes) : nullptr;
     for (int p = p0; p < p0 + pc; ++p) {
       const int ncopy = counts[p] < cap ? counts[p] : cap;
       if (counts[p] > cap) status = GPC_E_CAPACITY;
@@ -3195,7 +3192,7 @@ static int match_batch_unpacked(gpc_hip_ctx* c, const uint8_t* rawL, const uint8
     if (!land) return GPC_OK;
     const int p0 = k * chunk, pc = (p0 + chunk <= npairs) ? chunk : npairs - p0;
     HIPCHK(c, hipEventSynchronize(c->e_out[k & 1]));
-    const gpc_support* lslot = reinterpret_cast<const gpc_support*>((uint8_t*)c->h_stage + (size_t)(k & 1) * slot_bytes);
+    const gpc_support* lslot = reinterpret_cast<const gpc_support*>((uint8_t*)c->h_stage.p + (size_t)(k & 1) * slot_bytes);
     for (int p = p0; p < p0 + pc; ++p) {
       const int ncopy = counts[p] < cap ? counts[p] : cap;
       const size_t bytes = sizeof(gpc_support) * (size_t)ncopy, step = 256 * 1024;
@@ -3217,7 +3214,7 @@ static int match_batch_unpacked(gpc_hip_ctx* c, const uint8_t* rawL, const uint8
     if (k >= 2) HIPCHK(c, hipStreamWaitEvent(c->s_in, c->e_comp[slot], 0));  // chunk k-2 has read this slot
     const uint8_t *srcL = rawL + (size_t)p0 * n, *srcR = rawR + (size_t)p0 * n;
     if (bounce) {
-      uint8_t* bl = (uint8_t*)c->h_in + (size_t)slot * 2 * n * chunk;
+      uint8_t* bl = (uint8_t*)c->h_in.p + (size_t)slot * 2 * n * chunk;
       uint8_t* br = bl + n * chunk;
       if (k >= 2) HIPCHK(c, hipEventSynchronize(c->e_in[slot]));  // the upload of chunk k-2 has left this bounce slot
       const size_t bytes = n * pc, step = 256 * 1024;
@@ -3313,11 +3310,11 @@ int gpc_hip_match_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, 
   if (bounce) {  // pageable frames: two slots of the page-locked arena
     uint8_t* d_arena = nullptr;
     CHK(xfer_reserve(c, 2 * slot, &d_arena));
-    h_arena = c->h_xfer;
+    h_arena = c->h_xfer.p;
     CHK(ensure_pool(c));
   }
-  int32_t* hc = c->h_cnt;
-  int32_t* hn = c->h_cnt + npairs;
+  int32_t* hc = c->h_cnt.p;
+  int32_t* hn = c->h_cnt.p + npairs;
   gpc_correspondence* d_out = (gpc_correspondence*)c->out.p;
   auto first = [&](int k) { return k * step; };
   auto frames_of = [&](int k) { return nframes - first(k) < K ? nframes - first(k) : K; };
@@ -3600,12 +3597,12 @@ struct Stage {
       CHK(xfer_reserve(c, pieces * piece, &d_arena));
       CHK(ensure_pool(c));
       for (int k = 0; k < pieces; ++k)
-        if (!c->e_stage[k]) HIPCHK(c, hipEventCreateWithFlags(&c->e_stage[k], hipEventDisableTiming));
+        if (!c->e_stage[k]) HIPCHK(c, c->e_stage[k].create(hipEventDisableTiming));
     }
     for (size_t done = 0; done < n;) {
       if (at == piece) CHK(next_piece());
       const size_t nb = std::min(n - done, piece - at);
-      uint8_t* h = c->h_xfer + cur * piece + at;
+      uint8_t* h = c->h_xfer.p + cur * piece + at;
       host_copy(c, h, src + done, nb, true);
       host_copy_wait(c);
       HIPCHK(c, hipMemcpyAsync(p(region) + done, h, nb, hipMemcpyHostToDevice, c->stream));
@@ -3633,9 +3630,9 @@ struct Stage {
 
 // a chunk's scores -> the caller's array (120 bytes per pair: through h_cnt), then the chunk is done
 static int score_down(Stage& st, size_t region, gpc_score* scores, int n) {
-  CHK(st.down(st.c->h_cnt, region, sizeof(gpc_score) * (size_t)n));
+  CHK(st.down(st.c->h_cnt.p, region, sizeof(gpc_score) * (size_t)n));
   CHK(st.wait());
-  memcpy(scores, st.c->h_cnt, sizeof(gpc_score) * (size_t)n);
+  memcpy(scores, st.c->h_cnt.p, sizeof(gpc_score) * (size_t)n);
   return check_join_err(st.c);
 }
 
@@ -3828,7 +3825,7 @@ static int track_layout(Stage& st, size_t frame_bytes, int P, int cap, int track
 // rows.  corr, counts, ncand: null where the form does not hand them back
 static int track_down(Stage& st, const TrackRegions& r, int P, int cap, int track_cap, gpc_correspondence* corr, int32_t* counts,
                       int32_t* ncand, int32_t* next, int32_t* track_id, gpc_track* tracks, int32_t* ntracks) {
-  int32_t* hc = st.c->h_cnt;
+  int32_t* hc = st.c->h_cnt.p;
   CHK(st.down(hc, r.cnt, sizeof(int32_t) * (size_t)P));
   if (ncand) CHK(st.down(hc + P, r.nc, sizeof(int32_t) * (size_t)(P + 1)));
   CHK(st.down(hc + 2 * P + 1, r.nt, sizeof(int32_t)));
@@ -3896,13 +3893,13 @@ struct gpc_hip_track_stream {
   gpc::TrsBook book;
   gpc_settings settings;
   bool have_settings = false;
-  uint32_t* codes = nullptr;      // [H][W], allocated by the first push of frames
-  uint8_t* cand = nullptr;        // [H][W], allocated by the first push of frames under 32-bit Naive codes
-  int32_t* fstats = nullptr;      // GPC_STAT_STRIDE words
-  gpc::TrRec* crec = nullptr;     // [cap]
-  int32_t* cid = nullptr;         // [cap]
-  int32_t* words = nullptr;       // [0] the carried pair's count (clamped), [1] the number of tracks
-  gpc_track* table = nullptr;     // [max(track_cap, 1)]
+  DevBlock<uint32_t> codes;       // [H][W], allocated by the first push of frames
+  DevBlock<uint8_t> cand;         // [H][W], allocated by the first push of frames under 32-bit Naive codes
+  DevBlock<int32_t> fstats;       // GPC_STAT_STRIDE words
+  DevBlock<gpc::TrRec> crec;      // [cap]
+  DevBlock<int32_t> cid;          // [cap]
+  DevBlock<int32_t> words;        // [0] the carried pair's count (clamped), [1] the number of tracks
+  DevBlock<gpc_track> table;      // [max(track_cap, 1)]
   DevBuf nextw;                   // [c + k][cap] of the largest push so far
 };
 
@@ -3913,14 +3910,6 @@ int trs_check(gpc_hip_ctx* c, gpc_hip_track_stream* s) {
   for (gpc_hip_track_stream* t : c->track_streams)   // (a destroyed stream, or another context's, is not in the list)
     if (t == s) return GPC_OK;
   return GPC_E_INVALID;
-}
-
-void trs_free(gpc_hip_track_stream* s) {
-  void* mem[] = {s->codes, s->cand, s->fstats, s->crec, s->cid, s->words, s->table};
-  for (void* p : mem)
-    if (p) (void)hipFree(p);
-  release(s->nextw);
-  delete s;
 }
 
 // The link steps over the window [carried pair, k new pairs] whose new records are on the device, then the carry of the
@@ -3940,8 +3929,8 @@ int trs_link(gpc_hip_ctx* c, gpc_hip_track_stream* s, const gpc_correspondence* 
   int32_t* pred = (int32_t*)c->tr_pred.p;
   int32_t* blk = (int32_t*)c->tr_blk.p;
   int32_t* next = (int32_t*)s->nextw.p;
-  const int32_t* cm = s->words;
-  int32_t* total = s->words + 1;
+  const int32_t* cm = s->words.p;
+  int32_t* total = s->words.p + 1;
   const unsigned gx = (unsigned)(nchunk < 1024 ? nchunk : 1024);
   const dim3 sgrid(gx, k), wgrid(gx, cy + k), cgrid((unsigned)nchunk, cy + k);
   {
@@ -3955,7 +3944,7 @@ int trs_link(gpc_hip_ctx* c, gpc_hip_track_stream* s, const gpc_correspondence* 
   }
   {
     Timed t(c, KID_TRS_LINK);
-    hipLaunchKernelGGL(gpc::k_trs_link, wgrid, dim3(TR_THREADS), 0, c->stream, (const gpc::TrRec*)s->crec, cm, cy, rec, cap, d_counts,
+    hipLaunchKernelGGL(gpc::k_trs_link, wgrid, dim3(TR_THREADS), 0, c->stream, (const gpc::TrRec*)s->crec.p, cm, cy, rec, cap, d_counts,
                        W, H, k, (const int32_t*)plane, pred, next);
   }
   {
@@ -3969,23 +3958,17 @@ int trs_link(gpc_hip_ctx* c, gpc_hip_track_stream* s, const gpc_correspondence* 
   }
   {
     Timed t(c, KID_TRS_WALK);
-    hipLaunchKernelGGL(gpc::k_trs_walk, cgrid, dim3(TR_THREADS), 0, c->stream, cm, (const int32_t*)s->cid, cy, cap, d_counts, k,
+    hipLaunchKernelGGL(gpc::k_trs_walk, cgrid, dim3(TR_THREADS), 0, c->stream, cm, (const int32_t*)s->cid.p, cy, cap, d_counts, k,
                        (const int32_t*)pred, (const int32_t*)next, (const int32_t*)blk, (int)nchunk, s->book.pairs_seen, d_track_id,
-                       d_prev, (gpc::TrRow*)s->table, s->book.track_cap);
+                       d_prev, (gpc::TrRow*)s->table.p, s->book.track_cap);
   }
   {
     Timed t(c, KID_TRS_SAVE);
     hipLaunchKernelGGL(gpc::k_trs_save, dim3(gx), dim3(TR_THREADS), 0, c->stream, rec + (size_t)(k - 1) * cap,
-                       (const int32_t*)d_track_id + (size_t)(k - 1) * cap, d_counts + (k - 1), cap, s->crec, s->cid, s->words);
+                       (const int32_t*)d_track_id + (size_t)(k - 1) * cap, d_counts + (k - 1), cap, s->crec.p, s->cid.p, s->words.p);
   }
   for (int q = KID_TRS_FILL; q <= KID_TRS_SAVE; ++q) snprintf(c->launch_name[q], sizeof c->launch_name[0], "gpc::%s", kKernelNames[q]);
   HIPCHK(c, hipGetLastError());
-  return GPC_OK;
-}
-
-int trs_alloc(gpc_hip_ctx* c, void** p, size_t bytes) {
-  if (*p) return GPC_OK;
-  HIPCHK(c, hipMalloc(p, bytes));
   return GPC_OK;
 }
 
@@ -4009,9 +3992,9 @@ int trs_push_frames(gpc_hip_ctx* c, gpc_hip_track_stream* s, const uint8_t* d_fr
   const bool wide = wide_codes(c);
   HIPCHK(c, hipSetDevice(c->device));
   if (c->pipeline > 1) CHK(drain_lanes(c));  // (streams run on the context itself, as sequences do)
-  CHK(trs_alloc(c, (void**)&s->codes, sizeof(uint32_t) * n));
-  CHK(trs_alloc(c, (void**)&s->fstats, sizeof(int32_t) * GPC_STAT_STRIDE));
-  if (wide) CHK(trs_alloc(c, (void**)&s->cand, n));
+  if (!s->codes.p) HIPCHK(c, s->codes.alloc(sizeof(uint32_t) * n));
+  if (!s->fstats.p) HIPCHK(c, s->fstats.alloc(sizeof(int32_t) * GPC_STAT_STRIDE));
+  if (wide && !s->cand.p) HIPCHK(c, s->cand.alloc(n));
   CHK(ensure(c, c->codes, sizeof(uint32_t) * n * nimg));
   CHK(ensure(c, c->stats, sizeof(int32_t) * GPC_STAT_STRIDE * nimg));
   if (npairs > 0) CHK(ensure(c, c->sstats, sizeof(int32_t) * GPC_STAT_STRIDE * 2 * npairs));
@@ -4025,15 +4008,15 @@ int trs_push_frames(gpc_hip_ctx* c, gpc_hip_track_stream* s, const uint8_t* d_fr
     uint8_t* gr = (uint8_t*)c->grad.p + n * off;
     CHK(run_preprocess(c, d_frames, nullptr, W, H, nframes, 1, thr, false, sm, gr, stats + GPC_STAT_STRIDE * off));
     CHK(run_hash(c, sm, gr, nullptr, W, H, nframes, false, codes + n * off, 0, 2, stats + GPC_STAT_STRIDE * off));
-    if (off) CHK(dev_copy16(c, c->grad.p, s->cand, n));
+    if (off) CHK(dev_copy16(c, c->grad.p, s->cand.p, n));
   } else {
     CHK(run_preprocess(c, d_frames, nullptr, W, H, nframes, 1, thr, true, nullptr, nullptr, stats + GPC_STAT_STRIDE * off));
     CHK(run_hash(c, (const uint8_t*)c->smooth.p, (const uint8_t*)c->grad.p, nullptr, W, H, nframes, false, codes + n * off, 0, 2,
                  stats + GPC_STAT_STRIDE * off));
   }
   if (off) {
-    CHK(dev_copy16(c, codes, s->codes, sizeof(uint32_t) * n));
-    CHK(dev_copy16(c, stats, s->fstats, sizeof(int32_t) * GPC_STAT_STRIDE));
+    CHK(dev_copy16(c, codes, s->codes.p, sizeof(uint32_t) * n));
+    CHK(dev_copy16(c, stats, s->fstats.p, sizeof(int32_t) * GPC_STAT_STRIDE));
   }
   if (d_ncand) {
     Timed t(c, KID_TRS_NCAND);
@@ -4056,9 +4039,9 @@ int trs_push_frames(gpc_hip_ctx* c, gpc_hip_track_stream* s, const uint8_t* d_fr
   // the links first (their workspaces may still fail to grow, and nothing of the carry has been touched by then), then the
   // carry of the next push: the last frame's codes, statistics and (wide) candidate bytes
   if (npairs > 0) CHK(trs_link(c, s, d_corr, d_counts, p, d_prev, d_track_id));
-  CHK(dev_copy16(c, s->codes, codes + n * (size_t)(nimg - 1), sizeof(uint32_t) * n));
-  CHK(dev_copy16(c, s->fstats, stats + GPC_STAT_STRIDE * (nimg - 1), sizeof(int32_t) * GPC_STAT_STRIDE));
-  if (wide) CHK(dev_copy16(c, s->cand, (const uint8_t*)c->grad.p + n * (size_t)(nimg - 1), n));
+  CHK(dev_copy16(c, s->codes.p, codes + n * (size_t)(nimg - 1), sizeof(uint32_t) * n));
+  CHK(dev_copy16(c, s->fstats.p, stats + GPC_STAT_STRIDE * (nimg - 1), sizeof(int32_t) * GPC_STAT_STRIDE));
+  if (wide) CHK(dev_copy16(c, s->cand.p, (const uint8_t*)c->grad.p + n * (size_t)(nimg - 1), n));
   gpc::trs_commit(s->book, gpc::TRS_FRAMES, nframes, c->code_gen, p);
   return st;
 }
@@ -4066,7 +4049,7 @@ int trs_push_frames(gpc_hip_ctx* c, gpc_hip_track_stream* s, const uint8_t* d_fr
 // the running total, read back (the stream is waited for); tightens the bound on the ids
 int trs_total(gpc_hip_ctx* c, gpc_hip_track_stream* s, int32_t* total) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(total, s->words + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(total, s->words.p + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
   gpc::trs_tighten(s->book, *total);
   return GPC_OK;
 }
@@ -4084,13 +4067,12 @@ int gpc_hip_track_stream_create(gpc_hip_ctx* c, int W, int H, const gpc_settings
   s->book.W = W, s->book.H = H, s->book.cap = cap_per_pair, s->book.track_cap = track_cap;
   if (settings) s->settings = *settings, s->have_settings = true;
   const size_t cap = (size_t)cap_per_pair;
-  if (hipMalloc((void**)&s->crec, pad16(sizeof(gpc::TrRec) * cap)) != hipSuccess ||
-      hipMalloc((void**)&s->cid, pad16(sizeof(int32_t) * cap)) != hipSuccess || hipMalloc((void**)&s->words, 16) != hipSuccess ||
-      hipMalloc((void**)&s->table, sizeof(gpc_track) * (size_t)(track_cap > 0 ? track_cap : 1)) != hipSuccess ||
-      hipMemsetAsync(s->words, 0, 16, c->stream) != hipSuccess) {
+  if (s->crec.alloc(pad16(sizeof(gpc::TrRec) * cap)) != hipSuccess || s->cid.alloc(pad16(sizeof(int32_t) * cap)) != hipSuccess ||
+      s->words.alloc(16) != hipSuccess || s->table.alloc(sizeof(gpc_track) * (size_t)(track_cap > 0 ? track_cap : 1)) != hipSuccess ||
+      hipMemsetAsync(s->words.p, 0, 16, c->stream) != hipSuccess) {
     (void)hipGetLastError();
     snprintf(c->err, sizeof(c->err), "track stream of %d records per pair and %d rows: device allocation failed", cap_per_pair, track_cap);
-    trs_free(s);
+    delete s;
     return GPC_E_HIP;
   }
   c->track_streams.push_back(s);
@@ -4104,14 +4086,14 @@ int gpc_hip_track_stream_destroy(gpc_hip_ctx* c, gpc_hip_track_stream* s) {
   (void)hipStreamSynchronize(c->stream);
   for (size_t k = 0; k < c->track_streams.size(); ++k)
     if (c->track_streams[k] == s) { c->track_streams.erase(c->track_streams.begin() + k); break; }
-  trs_free(s);
+  delete s;
   return GPC_OK;
 }
 
 int gpc_hip_track_stream_reset(gpc_hip_ctx* c, gpc_hip_track_stream* s) {
   CHK(trs_check(c, s));
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemsetAsync(s->words, 0, 16, c->stream));  // (behind whatever a push has queued)
+  HIPCHK(c, hipMemsetAsync(s->words.p, 0, 16, c->stream));  // (behind whatever a push has queued)
   gpc::trs_reset(s->book);
   return GPC_OK;
 }
@@ -4158,10 +4140,10 @@ int gpc_hip_track_stream_push(gpc_hip_ctx* c, gpc_hip_track_stream* s, const uin
                                (int32_t*)st.p(r_nc), (int32_t*)st.p(r_prev), (int32_t*)st.p(r_id), p);
   if (status != GPC_OK && status != GPC_E_CAPACITY) return status;
   status = GPC_OK;
-  int32_t* hc = c->h_cnt;
+  int32_t* hc = c->h_cnt.p;
   if (k) CHK(st.down(hc, r_cnt, sizeof(int32_t) * (size_t)k));
   CHK(st.down(hc + k, r_nc, sizeof(int32_t) * (size_t)nframes));
-  HIPCHK(c, hipMemcpyAsync(hc + k + nframes, s->words + 1, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hc + k + nframes, s->words.p + 1, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   CHK(st.wait());
   for (int t = 0; t < k; ++t) {
     const size_t m = (size_t)valid_records(hc[t], cap), at = (size_t)t * cap;
@@ -4194,8 +4176,8 @@ int gpc_hip_track_stream_state(gpc_hip_ctx* c, gpc_hip_track_stream* s, int* fra
 
 int gpc_hip_track_stream_table(gpc_hip_track_stream* s, const gpc_track** d_tracks, const int32_t** d_ntracks) {
   if (!s || !d_tracks || !d_ntracks) return GPC_E_INVALID;
-  *d_tracks = s->table;
-  *d_ntracks = s->words + 1;
+  *d_tracks = s->table.p;
+  *d_ntracks = s->words.p + 1;
   return GPC_OK;
 }
 
@@ -4208,7 +4190,7 @@ int gpc_hip_track_stream_read_tracks(gpc_hip_ctx* c, gpc_hip_track_stream* s, in
   *n_tracks = total;
   CHK(gpc::trs_read_check(s->book, first, n));
   const long end = (long)first + n < total ? (long)first + n : total;  // rows at total and beyond do not exist yet
-  if (end > first) HIPCHK(c, hipMemcpy(out, s->table + first, sizeof(gpc_track) * (size_t)(end - first), hipMemcpyDeviceToHost));
+  if (end > first) HIPCHK(c, hipMemcpy(out, s->table.p + first, sizeof(gpc_track) * (size_t)(end - first), hipMemcpyDeviceToHost));
   return GPC_OK;
 }
 
@@ -4402,17 +4384,17 @@ static int cons_host(gpc_hip_ctx* c, const void* rec, int cap, const int32_t* co
     CHK(st.up_records(r_rec, rec, esz, cap, counts, p0, pc));
     CHK(cons_filter<CORR>(c, st.p(r_rec), cap, (const int32_t*)st.p(r_cnt), W, H, pc, prm, keep ? st.p(r_keep) : nullptr, st.p(r_out),
                           cap_out, index ? (int32_t*)st.p(r_idx) : nullptr, (int32_t*)st.p(r_n)));
-    CHK(st.down(c->h_cnt, r_n, sizeof(int32_t) * (size_t)pc));
+    CHK(st.down(c->h_cnt.p, r_n, sizeof(int32_t) * (size_t)pc));
     CHK(st.wait());
     for (int t = 0; t < pc; ++t) {  // a pair's keep bytes as far as its records go, its kept records and their indices as far as cap_out
-      const size_t m = (size_t)valid_records(counts[p0 + t], cap), w = (size_t)valid_records(c->h_cnt[t], cap_out), q = (size_t)(p0 + t);
-      if (c->h_cnt[t] > cap_out) status = GPC_E_CAPACITY;
+      const size_t m = (size_t)valid_records(counts[p0 + t], cap), w = (size_t)valid_records(c->h_cnt.p[t], cap_out), q = (size_t)(p0 + t);
+      if (c->h_cnt.p[t] > cap_out) status = GPC_E_CAPACITY;
       if (keep && m) CHK(st.down(keep + q * cap, r_keep + (size_t)t * cap, m));
       if (w) CHK(st.down((uint8_t*)out + esz * q * cap_out, r_out + esz * (size_t)t * cap_out, esz * w));
       if (w && index) CHK(st.down(index + q * cap_out, r_idx + sizeof(int32_t) * (size_t)t * cap_out, sizeof(int32_t) * w));
     }
     CHK(st.wait());
-    memcpy(out_counts + p0, c->h_cnt, sizeof(int32_t) * (size_t)pc);
+    memcpy(out_counts + p0, c->h_cnt.p, sizeof(int32_t) * (size_t)pc);
   }
   CHK(check_join_err(c));
   return status;
@@ -4800,7 +4782,7 @@ static int pyr_host(gpc_hip_ctx* c, const uint8_t* a, const uint8_t* b, int W, i
     if (!CORR) CHK(st.up(r_b, b + n * p0, n * pc));
     CHK(pyr_match<CORR>(c, st.p(r_a), CORR ? nullptr : st.p(r_b), W, H, pc, levels, s, st.p(r_out), cap, (int32_t*)st.p(r_cnt),
                         (int32_t*)st.p(r_lc), (int32_t*)st.p(r_nc)));
-    int32_t *h_n = c->h_cnt, *h_lc = h_n + K, *h_nc = h_lc + (size_t)levels * K;
+    int32_t *h_n = c->h_cnt.p, *h_lc = h_n + K, *h_nc = h_lc + (size_t)levels * K;
     CHK(st.down(h_n, r_cnt, sizeof(int32_t) * (size_t)pc));
     CHK(st.down(h_lc, r_lc, sizeof(int32_t) * (size_t)levels * pc));
     CHK(st.down(h_nc, r_nc, sizeof(int32_t) * levels * cs));
@@ -4888,7 +4870,7 @@ static int match_batch_direct(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t
   CHK(ensure(c, c->codes, sizeof(uint32_t) * n * 2 * npairs));
   CHK(pinned_counts(c, npairs));
   int32_t* d_cnt = nullptr;
-  HIPCHK(c, hipHostGetDevicePointer((void**)&d_cnt, c->h_cnt, 0));
+  HIPCHK(c, hipHostGetDevicePointer((void**)&d_cnt, c->h_cnt.p, 0));
   uint8_t* d_l = (uint8_t*)c->raw.p;
   uint8_t* d_r = d_l + n * npairs;
   // Page-locked images are fetched by a kernel (one launch, both sides) instead of two copy-engine submissions; the
@@ -4909,8 +4891,8 @@ static int match_batch_direct(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t
     uint8_t* d_arena = nullptr;
     const size_t side = pad16(n * npairs);
     CHK(xfer_reserve(c, 2 * side, &d_arena));
-    memcpy(c->h_xfer, rawL, n * npairs);
-    memcpy(c->h_xfer + side, rawR, n * npairs);
+    memcpy(c->h_xfer.p, rawL, n * npairs);
+    memcpy(c->h_xfer.p + side, rawR, n * npairs);
     const unsigned n16 = (unsigned)(side / 16);
     CHK(ensure(c, c->raw, 2 * side));
     d_l = (uint8_t*)c->raw.p;
@@ -4926,11 +4908,11 @@ static int match_batch_direct(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t
   CHK(check_join_err(c));
   int status = GPC_OK;
   for (int p = 0; p < npairs; ++p) {
-    counts[p] = c->h_cnt[p];
+    counts[p] = c->h_cnt.p[p];
     if (counts[p] > cap) status = GPC_E_CAPACITY;
     if (ncand) {
-      ncand[2 * p] = c->h_cnt[npairs + 2 * p];
-      ncand[2 * p + 1] = c->h_cnt[npairs + 2 * p + 1];
+      ncand[2 * p] = c->h_cnt.p[npairs + 2 * p];
+      ncand[2 * p + 1] = c->h_cnt.p[npairs + 2 * p + 1];
     }
   }
   return status;
@@ -5033,17 +5015,13 @@ static int match_batch_packed(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t
   CHK(ensure(c, c->counts, sizeof(int32_t) * npairs));
   CHK(ensure(c, c->ncand, sizeof(int32_t) * 2 * npairs));
   const size_t stage_bytes = 4 * cb;
-  if (stage_bytes > c->h_stage_cap) {
+  if (stage_bytes > c->h_stage.cap) {
     c->pool.wait_all();
-    if (c->h_stage) HIPCHK(c, hipHostFree(c->h_stage));
-    c->h_stage = nullptr;
-    c->h_stage_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->h_stage, stage_bytes, hipHostMallocDefault));
-    c->h_stage_cap = stage_bytes;
+    CHK(ensure_pinned(c, c->h_stage, stage_bytes));
   }
   CHK(pinned_counts(c, npairs));
-  int32_t* hc = c->h_cnt;               // counts
-  int32_t* hn = c->h_cnt + npairs;      // candidate counts
+  int32_t* hc = c->h_cnt.p;               // counts
+  int32_t* hn = c->h_cnt.p + npairs;      // candidate counts
   CHK(batch_streams(c));
   // Pageable input images (malloc, std::vector, ndb::Buffer): a copy engine cannot read them, and hipMemcpyAsync then stages
   // them itself, synchronously, on the calling thread -- which serialised the whole chunk pipeline (32 pairs: 7.5 ms
@@ -5055,13 +5033,9 @@ static int match_batch_packed(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t
   const bool bounce = !device_view_of_host(rawL) || !device_view_of_host(rawR);
   if (bounce) {
     const size_t need = 2 * 2 * n * (size_t)chunk;
-    if (need > c->h_in_cap) {
+    if (need > c->h_in.cap) {
       HIPCHK(c, hipStreamSynchronize(c->s_in));
-      if (c->h_in) HIPCHK(c, hipHostFree(c->h_in));
-      c->h_in = nullptr;
-      c->h_in_cap = 0;
-      HIPCHK(c, hipHostMalloc(&c->h_in, need, hipHostMallocDefault));
-      c->h_in_cap = need;
+      CHK(ensure_pinned(c, c->h_in, need));
     }
   }
   {  // numThreads_ of the reference's settings asks for that many workers; otherwise what the process may use
@@ -5072,7 +5046,7 @@ static int match_batch_packed(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t
     c->pool.start(nt, c->have_node_cpus ? &c->node_cpus : nullptr, &c->node_l3);
   }
   uint8_t* d_pk = (uint8_t*)c->packed.p;
-  uint8_t* h_pk = (uint8_t*)c->h_stage;
+  uint8_t* h_pk = (uint8_t*)c->h_stage.p;
   int status = GPC_OK;
   int32_t* d_tot = reinterpret_cast<int32_t*>(d_pk + 3 * cb);  // [3][chunk] scratch of k_pair_totals
   // the counts of chunk k are on their way: wait for them, then fetch the chunk's row counts and records in one copy
@@ -5141,7 +5115,7 @@ static int match_batch_packed(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t
     if (k >= 2) HIPCHK(c, hipStreamWaitEvent(c->s_in, c->e_comp[(k - 2) & 3], 0));  // chunk k-2 has read this slot
     const uint8_t *srcL = rawL + (size_t)p0 * n, *srcR = rawR + (size_t)p0 * n;
     if (bounce) {
-      uint8_t* bl = (uint8_t*)c->h_in + (size_t)(k & 1) * 2 * n * chunk;
+      uint8_t* bl = (uint8_t*)c->h_in.p + (size_t)(k & 1) * 2 * n * chunk;
       uint8_t* br = bl + n * chunk;
       if (k >= 2) HIPCHK(c, hipEventSynchronize(c->e_in[(k - 2) & 3]));  // the upload of chunk k-2 has left this bounce slot
       const int pieces = c->pool.size() > 1 ? c->pool.size() : 1;
@@ -5246,14 +5220,14 @@ int gpc_hip_match_pair_begin(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t*
   CHK(ensure(c, c->codes, sizeof(uint32_t) * n * 2));
   CHK(pinned_counts(c, 1));
   int32_t* d_cnt = nullptr;
-  HIPCHK(c, hipHostGetDevicePointer((void**)&d_cnt, c->h_cnt, 0));
+  HIPCHK(c, hipHostGetDevicePointer((void**)&d_cnt, c->h_cnt.p, 0));
   uint8_t* d_arena = nullptr;
   CHK(xfer_reserve(c, out_bytes + 2 * n, &d_arena));
   const uint8_t* vL = static_cast<const uint8_t*>(device_view_of_host(rawL));
   const uint8_t* vR = vL ? static_cast<const uint8_t*>(device_view_of_host(rawR)) : nullptr;
   if (!vL || !vR || (((uintptr_t)vL | (uintptr_t)vR) & 15u)) {
-    memcpy(c->h_xfer + out_bytes, rawL, n);
-    memcpy(c->h_xfer + out_bytes + n, rawR, n);
+    memcpy(c->h_xfer.p + out_bytes, rawL, n);
+    memcpy(c->h_xfer.p + out_bytes + n, rawR, n);
     vL = d_arena + out_bytes;
     vR = vL + n;
   }
@@ -5335,11 +5309,11 @@ int gpc_hip_warmup(gpc_hip_ctx* c, int W, int H, const gpc_settings* settings) {
     return h;
   };
   // page-locked images and results: the single-pair path of gpc_hip_match_batch that Forest::matchPair takes
-  uint8_t* pin = nullptr;
+  Pinned<uint8_t> pin;  // (freed on every return)
   const size_t cap = n / 2 + 1;
-  HIPCHK(c, hipHostMalloc((void**)&pin, 2 * n + sizeof(gpc_support) * cap, hipHostMallocDefault));
-  uint8_t *L = pin, *R = pin + n;
-  gpc_support* pout = reinterpret_cast<gpc_support*>(pin + 2 * n);
+  CHK(ensure_pinned(c, pin, 2 * n + sizeof(gpc_support) * cap));
+  uint8_t *L = pin.p, *R = pin.p + n;
+  gpc_support* pout = reinterpret_cast<gpc_support*>(pin.p + 2 * n);
   for (int y = 0; y < H; ++y)
     for (int x = 0; x < W + 8; ++x) {
       const uint8_t v = (uint8_t)((((mix((uint32_t)x >> 2, (uint32_t)y >> 2) & 0xFF) * 3 + (mix((uint32_t)x, (uint32_t)y) & 0x3F)) >> 2));
@@ -5389,7 +5363,6 @@ int gpc_hip_warmup(gpc_hip_ctx* c, int W, int H, const gpc_settings* settings) {
     std::lock_guard<std::mutex> g(g_res_mu);  // the host copies die with this scope
     c->res[0].valid = c->res[1].valid = false;
   }
-  (void)hipHostFree(pin);
   return st;
 }
 
@@ -5417,17 +5390,8 @@ int train_check(gpc_hip_ctx* c, gpc_hip_train_set* t) {
 }
 
 int train_scratch(gpc_hip_ctx* c, gpc_hip_train_set* t, size_t ncounts, size_t ncand) {
-  if (ncounts > t->counts_cap) {
-    if (t->counts) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(t->counts)); t->counts = nullptr; }
-    HIPCHK(c, hipMalloc((void**)&t->counts, sizeof(int32_t) * ncounts));
-    t->counts_cap = ncounts;
-  }
-  if (ncand > t->cand_cap) {
-    if (t->d_cand) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(t->d_cand)); t->d_cand = nullptr; }
-    HIPCHK(c, hipMalloc((void**)&t->d_cand, sizeof(gpc::GpcSplit) * ncand));
-    t->cand_cap = ncand;
-  }
-  return GPC_OK;
+  CHK(ensure(c, t->counts, sizeof(int32_t) * ncounts));
+  return ensure(c, t->d_cand, sizeof(gpc::GpcSplit) * ncand);
 }
 
 bool split_ok(const gpc_split& p) { return p.i >= 0 && p.i < TS_PATCH && p.j >= 0 && p.j < TS_PATCH; }
@@ -5438,34 +5402,26 @@ int gpc_hip_train_set_create(gpc_hip_ctx* c, const uint8_t* triplets, int n, gpc
   if (!c || !triplets || n <= 0 || !out) return GPC_E_INVALID;
   *out = nullptr;
   HIPCHK(c, hipSetDevice(c->device));
-  gpc_hip_train_set* t = new gpc_hip_train_set();
+  std::unique_ptr<gpc_hip_train_set> t(new gpc_hip_train_set());  // (every early return frees the set and d_aos)
   t->owner = c;
   t->n = n;
   t->np = ((long)n + 255) / 256 * 256;
-  uint8_t* d_aos = nullptr;
+  DevBlock<uint8_t> d_aos;
   const size_t bytes = (size_t)n * 3 * TS_PATCH;
-  auto fail = [&](int st) {
-    if (d_aos) (void)hipFree(d_aos);
-    if (t->planes) (void)hipFree(t->planes);
-    if (t->flags) (void)hipFree(t->flags);
-    delete t;
-    return st;
-  };
-  if (hipMalloc((void**)&d_aos, bytes) != hipSuccess || hipMalloc((void**)&t->planes, (size_t)3 * TS_PATCH * t->np) != hipSuccess ||
-      hipMalloc((void**)&t->flags, (size_t)t->np) != hipSuccess) {
+  if (d_aos.alloc(bytes) != hipSuccess || t->planes.alloc((size_t)3 * TS_PATCH * t->np) != hipSuccess ||
+      t->flags.alloc((size_t)t->np) != hipSuccess) {
     snprintf(c->err, sizeof(c->err), "training set of %d triplets: device allocation failed", n);
-    return fail(GPC_E_HIP);
+    return GPC_E_HIP;
   }
-  if (hipMemcpyAsync(d_aos, triplets, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(GPC_E_HIP);
+  if (hipMemcpyAsync(d_aos.p, triplets, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return GPC_E_HIP;
   hipLaunchKernelGGL(gpc::k_ts_transpose, dim3((unsigned)(t->np / 64), 3, 3), dim3(TS_THREADS), 0, c->stream,
-                     (const uint8_t*)d_aos, n, t->np, t->planes);
-  if (hipMemsetAsync(t->flags, 0, (size_t)t->np, c->stream) != hipSuccess) return fail(GPC_E_HIP);
-  hipLaunchKernelGGL(gpc::k_ts_begin, dim3((unsigned)(t->np / TS_THREADS)), dim3(TS_THREADS), 0, c->stream, t->flags, n,
+                     (const uint8_t*)d_aos.p, n, t->np, t->planes.p);
+  if (hipMemsetAsync(t->flags.p, 0, (size_t)t->np, c->stream) != hipSuccess) return GPC_E_HIP;
+  hipLaunchKernelGGL(gpc::k_ts_begin, dim3((unsigned)(t->np / TS_THREADS)), dim3(TS_THREADS), 0, c->stream, t->flags.p, n,
                      t->np, 1);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return fail(GPC_E_HIP);
-  (void)hipFree(d_aos);
-  c->train_sets.push_back(t);
-  *out = t;
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return GPC_E_HIP;
+  c->train_sets.push_back(t.get());
+  *out = t.release();
   return GPC_OK;
 }
 
@@ -5475,10 +5431,6 @@ int gpc_hip_train_set_destroy(gpc_hip_ctx* c, gpc_hip_train_set* t) {
   (void)hipStreamSynchronize(c->stream);
   for (size_t k = 0; k < c->train_sets.size(); ++k)
     if (c->train_sets[k] == t) { c->train_sets.erase(c->train_sets.begin() + k); break; }
-  if (t->planes) (void)hipFree(t->planes);
-  if (t->flags) (void)hipFree(t->flags);
-  if (t->counts) (void)hipFree(t->counts);
-  if (t->d_cand) (void)hipFree(t->d_cand);
   delete t;
   return GPC_OK;
 }
@@ -5487,20 +5439,20 @@ int gpc_hip_train_set_size(const gpc_hip_train_set* t) { return t ? t->n : 0; }
 
 int gpc_hip_train_set_marks(gpc_hip_ctx* c, gpc_hip_train_set* t, const uint8_t* marks_in, uint8_t* marks_out) {
   CHK(train_check(c, t));
-  uint8_t* d_m = nullptr;
-  HIPCHK(c, hipMalloc((void**)&d_m, (size_t)t->n));
+  DevBlock<uint8_t> d_mem;  // (freed on every return)
+  HIPCHK(c, d_mem.alloc((size_t)t->n));
+  uint8_t* d_m = d_mem.p;
   const dim3 grid((unsigned)((t->n + TS_THREADS - 1) / TS_THREADS));
   int st = GPC_OK;
   if (marks_in) {
     if (hipMemcpyAsync(d_m, marks_in, (size_t)t->n, hipMemcpyHostToDevice, c->stream) != hipSuccess) st = GPC_E_HIP;
-    hipLaunchKernelGGL(gpc::k_ts_set_marks, grid, dim3(TS_THREADS), 0, c->stream, t->flags, (const uint8_t*)d_m, t->n);
+    hipLaunchKernelGGL(gpc::k_ts_set_marks, grid, dim3(TS_THREADS), 0, c->stream, t->flags.p, (const uint8_t*)d_m, t->n);
   }
   if (marks_out && st == GPC_OK) {
-    hipLaunchKernelGGL(gpc::k_ts_get_marks, grid, dim3(TS_THREADS), 0, c->stream, (const uint8_t*)t->flags, d_m, t->n);
+    hipLaunchKernelGGL(gpc::k_ts_get_marks, grid, dim3(TS_THREADS), 0, c->stream, (const uint8_t*)t->flags.p, d_m, t->n);
     if (hipMemcpyAsync(marks_out, d_m, (size_t)t->n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) st = GPC_E_HIP;
   }
   if (hipStreamSynchronize(c->stream) != hipSuccess) st = GPC_E_HIP;
-  (void)hipFree(d_m);
   if (st != GPC_OK) snprintf(c->err, sizeof(c->err), "training set marks: HIP copy failed");
   return st;
 }
@@ -5514,13 +5466,13 @@ int gpc_hip_train_eval_split(gpc_hip_ctx* c, gpc_hip_train_set* t, const gpc_spl
   for (int l = 0; l < np_; ++l)
     if (!split_ok(params[l])) return GPC_E_INVALID;
   CHK(train_scratch(c, t, 4, 64));
-  HIPCHK(c, hipMemcpyAsync(t->d_cand, params, sizeof(gpc_split) * np_, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(t->counts, 0, sizeof(int32_t) * 4, c->stream));
+  HIPCHK(c, hipMemcpyAsync(t->d_cand.p, params, sizeof(gpc_split) * np_, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(t->counts.p, 0, sizeof(int32_t) * 4, c->stream));
   hipLaunchKernelGGL((gpc::k_ts_eval_split<false>), dim3((unsigned)(t->np / TS_THREADS)), dim3(TS_THREADS), 0, c->stream,
-                     (const uint8_t*)t->planes, t->flags, t->n, t->np, (const gpc::GpcSplit*)t->d_cand, np_, t->counts);
+                     (const uint8_t*)t->planes.p, t->flags.p, t->n, t->np, (const gpc::GpcSplit*)t->d_cand.p, np_, t->counts.p);
   HIPCHK(c, hipGetLastError());
   int32_t h[4];
-  HIPCHK(c, hipMemcpyAsync(h, t->counts, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h, t->counts.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   split_stats(h[0], h[1], h[2], h[3], w1, stats);
   return GPC_OK;
@@ -5533,9 +5485,9 @@ int gpc_hip_train_mark_split_samples(gpc_hip_ctx* c, gpc_hip_train_set* t, const
   for (int l = 0; l < num_params; ++l)
     if (!split_ok(params[l])) return GPC_E_INVALID;
   CHK(train_scratch(c, t, 4, 64));
-  if (num_params) HIPCHK(c, hipMemcpyAsync(t->d_cand, params, sizeof(gpc_split) * num_params, hipMemcpyHostToDevice, c->stream));
+  if (num_params) HIPCHK(c, hipMemcpyAsync(t->d_cand.p, params, sizeof(gpc_split) * num_params, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL((gpc::k_ts_eval_split<true>), dim3((unsigned)(t->np / TS_THREADS)), dim3(TS_THREADS), 0, c->stream,
-                     (const uint8_t*)t->planes, t->flags, t->n, t->np, (const gpc::GpcSplit*)t->d_cand, num_params,
+                     (const uint8_t*)t->planes.p, t->flags.p, t->n, t->np, (const gpc::GpcSplit*)t->d_cand.p, num_params,
                      (int32_t*)nullptr);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));  // params may be freed by the caller
@@ -5544,7 +5496,7 @@ int gpc_hip_train_mark_split_samples(gpc_hip_ctx* c, gpc_hip_train_set* t, const
 
 int gpc_hip_train_begin_fern(gpc_hip_ctx* c, gpc_hip_train_set* t, int reset_marks) {
   CHK(train_check(c, t));
-  hipLaunchKernelGGL(gpc::k_ts_begin, dim3((unsigned)(t->np / TS_THREADS)), dim3(TS_THREADS), 0, c->stream, t->flags, t->n,
+  hipLaunchKernelGGL(gpc::k_ts_begin, dim3((unsigned)(t->np / TS_THREADS)), dim3(TS_THREADS), 0, c->stream, t->flags.p, t->n,
                      t->np, reset_marks);
   HIPCHK(c, hipGetLastError());
   return GPC_OK;
@@ -5560,8 +5512,8 @@ int gpc_hip_train_eval_level(gpc_hip_ctx* c, gpc_hip_train_set* t, const gpc_spl
     if (!split_ok(cand[k])) return GPC_E_INVALID;
   const size_t nc = (size_t)ncand * ntau;
   CHK(train_scratch(c, t, 2 * nc + 1, (size_t)ncand));
-  HIPCHK(c, hipMemcpyAsync(t->d_cand, cand, sizeof(gpc_split) * ncand, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(t->counts, 0, sizeof(int32_t) * (2 * nc + 1), c->stream));
+  HIPCHK(c, hipMemcpyAsync(t->d_cand.p, cand, sizeof(gpc_split) * ncand, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(t->counts.p, 0, sizeof(int32_t) * (2 * nc + 1), c->stream));
   {
     Timed tm(c, KID_TRAIN_EVAL);
     // longest chunks that still leave >= 4096 workgroups (16 per CU); measured on 1 Mi triplets: 16 Ki-triplet
@@ -5570,15 +5522,15 @@ int gpc_hip_train_eval_level(gpc_hip_ctx* c, gpc_hip_train_set* t, const gpc_spl
     while (iters > 4 && ((t->np + (long)iters * TS_ITER - 1) / ((long)iters * TS_ITER)) * ncand < 4096) iters >>= 1;
     const unsigned chunks = (unsigned)((t->np + (long)iters * TS_ITER - 1) / ((long)iters * TS_ITER));
     hipLaunchKernelGGL(gpc::k_ts_eval_level, dim3(chunks, ncand), dim3(TS_THREADS), 0,
-                       c->stream, (const uint8_t*)t->planes, (const uint8_t*)t->flags, t->np,
-                       (const gpc::GpcSplit*)t->d_cand, taulo, ntau, iters, t->counts, t->counts + nc);
+                       c->stream, (const uint8_t*)t->planes.p, (const uint8_t*)t->flags.p, t->np,
+                       (const gpc::GpcSplit*)t->d_cand.p, taulo, ntau, iters, t->counts.p, t->counts.p + nc);
   }
   hipLaunchKernelGGL(gpc::k_ts_tot, dim3((unsigned)((t->np / 4 + TS_THREADS - 1) / TS_THREADS)), dim3(TS_THREADS), 0,
-                     c->stream, (const uint8_t*)t->flags, t->np, t->counts + 2 * nc);
+                     c->stream, (const uint8_t*)t->flags.p, t->np, t->counts.p + 2 * nc);
   HIPCHK(c, hipGetLastError());
   // one copy back: [tp | fp | tot] are contiguous on the device
   t->h_counts.resize(2 * nc + 1);
-  HIPCHK(c, hipMemcpyAsync(t->h_counts.data(), t->counts, sizeof(int32_t) * (2 * nc + 1), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(t->h_counts.data(), t->counts.p, sizeof(int32_t) * (2 * nc + 1), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   memcpy(tp, t->h_counts.data(), sizeof(int32_t) * nc);
   memcpy(fp, t->h_counts.data() + nc, sizeof(int32_t) * nc);
@@ -5591,7 +5543,7 @@ int gpc_hip_train_commit_level(gpc_hip_ctx* c, gpc_hip_train_set* t, const gpc_s
   if (!best || !split_ok(*best)) return GPC_E_INVALID;
   gpc::GpcSplit b = {best->i, best->j, best->tau};
   hipLaunchKernelGGL(gpc::k_ts_commit, dim3((unsigned)(t->np / TS_THREADS)), dim3(TS_THREADS), 0, c->stream,
-                     (const uint8_t*)t->planes, t->flags, t->n, t->np, b, mark_split);
+                     (const uint8_t*)t->planes.p, t->flags.p, t->n, t->np, b, mark_split);
   HIPCHK(c, hipGetLastError());
   return GPC_OK;
 }
@@ -5755,20 +5707,18 @@ static int extract_triplets(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* 
   // about 4 x 64 MiB at the default chunk size) are given back when the call ends; the page-locked transfer arena is the
   // context's, shared with the other host-buffer entry points, and stays
   auto release_ws = [c]() {
-    release(c->ext_raw);
-    release(c->ext_smooth);
-    release(c->ext_grad);
-    release(c->ext_groups);
+    (void)c->ext_raw.reset();
+    (void)c->ext_smooth.reset();
+    (void)c->ext_grad.reset();
+    (void)c->ext_groups.reset();
   };
   auto fail = [&](int st) {
     (void)hipStreamSynchronize(c->stream);
     release_ws();
-    if (t->planes) (void)hipFree(t->planes);
-    if (t->flags) (void)hipFree(t->flags);
     delete t;
     return st;
   };
-  if (hipMalloc((void**)&t->planes, (size_t)3 * TS_PATCH * np) != hipSuccess || hipMalloc((void**)&t->flags, (size_t)np) != hipSuccess) {
+  if (t->planes.alloc((size_t)3 * TS_PATCH * np) != hipSuccess || t->flags.alloc((size_t)np) != hipSuccess) {
     snprintf(c->err, sizeof(c->err), "training set of %d triplets: device allocation failed", n);
     return fail(GPC_E_HIP);
   }
@@ -5787,12 +5737,12 @@ static int extract_triplets(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* 
     if ((st = ensure(c, c->ext_smooth, 2 * side_bytes)) != GPC_OK || (st = ensure(c, c->ext_grad, 2 * side_bytes)) != GPC_OK ||
         (st = ensure(c, c->ext_groups, group_bytes)) != GPC_OK)
       return fail(st);
-    memcpy(c->h_xfer, gl.data(), sizeof(gpc::ExGroup) * gl.size());
+    memcpy(c->h_xfer.p, gl.data(), sizeof(gpc::ExGroup) * gl.size());
     const uint8_t *d_L = rawL + f0 * npx, *d_R = rawR + f0 * npx;
     if (!on_device) {
       if ((st = ensure(c, c->ext_raw, 2 * side_bytes)) != GPC_OK) return fail(st);
-      memcpy(c->h_xfer + group_bytes, rawL + f0 * npx, side_bytes);
-      memcpy(c->h_xfer + group_bytes + side_bytes, rawR + f0 * npx, side_bytes);
+      memcpy(c->h_xfer.p + group_bytes, rawL + f0 * npx, side_bytes);
+      memcpy(c->h_xfer.p + group_bytes + side_bytes, rawR + f0 * npx, side_bytes);
       if ((st = dev_copy16(c, c->ext_raw.p, d_arena + group_bytes, 2 * side_bytes)) != GPC_OK) return fail(st);
       d_L = (const uint8_t*)c->ext_raw.p;
       d_R = d_L + side_bytes;
@@ -5803,11 +5753,11 @@ static int extract_triplets(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* 
     if (st != GPC_OK) return fail(st);
     const unsigned nblk = (unsigned)((gl.size() + EX_GROUPS - 1) / EX_GROUPS);
     hipLaunchKernelGGL(gpc::k_extract_gather, dim3(nblk, 3, 3), dim3(TS_THREADS), 0, c->stream, (const uint8_t*)c->ext_smooth.p, W,
-                       (const gpc::ExGroup*)c->ext_groups.p, (int)gl.size(), np, t->planes);
+                       (const gpc::ExGroup*)c->ext_groups.p, (int)gl.size(), np, t->planes.p);
     if (hipGetLastError() != hipSuccess) return fail(GPC_E_HIP);
   }
-  if (hipMemsetAsync(t->flags, 0, (size_t)np, c->stream) != hipSuccess) return fail(GPC_E_HIP);
-  hipLaunchKernelGGL(gpc::k_ts_begin, dim3((unsigned)(np / TS_THREADS)), dim3(TS_THREADS), 0, c->stream, t->flags, n, np, 1);
+  if (hipMemsetAsync(t->flags.p, 0, (size_t)np, c->stream) != hipSuccess) return fail(GPC_E_HIP);
+  hipLaunchKernelGGL(gpc::k_ts_begin, dim3((unsigned)(np / TS_THREADS)), dim3(TS_THREADS), 0, c->stream, t->flags.p, n, np, 1);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return fail(GPC_E_HIP);
   release_ws();
   c->train_sets.push_back(t);
@@ -5837,11 +5787,11 @@ int gpc_hip_train_set_read(gpc_hip_ctx* c, gpc_hip_train_set* t, int first, int 
     const size_t bytes = (size_t)m * 3 * TS_PATCH;
     uint8_t* d_arena = nullptr;
     CHK(xfer_reserve(c, bytes, &d_arena));
-    hipLaunchKernelGGL(gpc::k_ts_read, dim3((unsigned)((m + 63) / 64), 3, 3), dim3(TS_THREADS), 0, c->stream, (const uint8_t*)t->planes,
+    hipLaunchKernelGGL(gpc::k_ts_read, dim3((unsigned)((m + 63) / 64), 3, 3), dim3(TS_THREADS), 0, c->stream, (const uint8_t*)t->planes.p,
                        t->np, first + done, m, d_arena);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    memcpy(aos + (size_t)done * 3 * TS_PATCH, c->h_xfer, bytes);
+    memcpy(aos + (size_t)done * 3 * TS_PATCH, c->h_xfer.p, bytes);
   }
   return GPC_OK;
 }
@@ -5897,6 +5847,14 @@ extern "C" int gpc_hip_debug_fingerprint(const uint8_t* smooth, const uint8_t* g
   if (!smooth || !grad || !fp || n_mask < 0 || (n_mask > 0 && !mask)) return GPC_E_INVALID;
   *fp = fingerprint(smooth, grad, n, mask, n_mask, full != 0);
   if (overlap) *overlap = ranges_overlap(a, na, b, nb) ? 1 : 0;
+  return GPC_OK;
+}
+
+// What the owners hold, over every context of the process (tests/test_gpu_resources.py): live device blocks, their bytes,
+// live page-locked blocks, live streams + events.  What callers own through gpc_hip_host_alloc is not counted.
+extern "C" int gpc_hip_debug_live_resources(uint64_t out[4]) {
+  if (!out) return GPC_E_INVALID;
+  for (int i = 0; i < 4; ++i) out[i] = g_live[i].load();
   return GPC_OK;
 }
 
@@ -5961,7 +5919,7 @@ int gpc_hip_reset_kernel_timing(gpc_hip_ctx* c) {
   if (!c) return GPC_E_INVALID;
   CHK(drain_lanes(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (auto& s : c->spans) c->free_spans.push_back(s);
+  for (auto& s : c->spans) c->free_spans.push_back(std::move(s));
   c->spans.clear();
   return GPC_OK;
 }

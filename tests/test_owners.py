@@ -1,0 +1,47 @@
+"""Who frees what: the owner types of opengpc_amd/csrc/owners.h driven by a stand-alone program with a recording
+backend under AddressSanitizer and UBSan, and a source check that gpc_hip.hip releases nothing by hand."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+CSRC = os.path.join(ROOT, "opengpc_amd", "csrc")
+
+
+@pytest.mark.skipif(not os.path.exists(CLANG), reason="needs the ROCm toolchain's clang++")
+def test_owners_under_asan_ubsan(tmp_path):
+    """exactly one release per allocation through destruction, moves, self-move, std::swap, reset and failed allocations,
+    for the block and the handle owner; allocations equal releases at exit (and the leak checker agrees)"""
+    exe = str(tmp_path / "owners_check")
+    subprocess.check_call([CLANG, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-Wall", "-Werror", "-I" + CSRC, "-o", exe,
+                           os.path.join(ROOT, "tests", "cpp", "owners_check.cpp")])
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0 and res.stdout.strip() == "ok", (res.returncode, res.stdout, res.stderr)
+
+
+def test_owners_header_is_host_only():
+    text = open(os.path.join(CSRC, "owners.h")).read()
+    assert not re.search(r"#\s*include\s*[<\"]hip", text)
+
+
+def test_nothing_is_released_by_hand():
+    """hipFree, hipHostFree, hipStreamDestroy and hipEventDestroy are called by the owners' HIP backends (the structs DevMem,
+    PinnedMem, StreamApi, EventApi) and by gpc_hip_host_free, which frees what the caller owns -- nowhere else"""
+    text = open(os.path.join(CSRC, "gpc_hip.hip")).read()
+    allowed = {"hipFree(": "DevMem", "hipHostFree(": "PinnedMem", "hipStreamDestroy(": "StreamApi", "hipEventDestroy(": "EventApi"}
+    # the body each call may stand in: from the opening line of the struct / function to the first line that is just a brace
+    def body(opening):
+        at = text.index(opening)
+        return at, at + re.search(r"^\};?$", text[at:], flags=re.M).end()
+    for call, backend in allowed.items():
+        spans = [body("struct %s {" % backend)]
+        if call == "hipHostFree(":
+            spans.append(body("int gpc_hip_host_free("))
+        hits = [m.start() for m in re.finditer(r"\b" + re.escape(call), text)]
+        assert hits, call
+        for h in hits:
+            assert any(a <= h < b for a, b in spans), "%s at line %d" % (call, text.count("\n", 0, h) + 1)
