@@ -872,6 +872,84 @@ int gpc_hip_pyramid_sequence(gpc_hip_ctx* ctx, const uint8_t* frames, int width,
                              const gpc_settings* settings, gpc_correspondence* out, int cap_per_pair, int32_t* counts,
                              int32_t* level_counts, int32_t* ncand);
 
+/* ---- dense maps from sparse matches: hierarchical fill ---------------------------------- */
+/* Every call above ends in a record list; these end in a FIELD: one disparity, or one (u, v), per pixel, in 1/256 pixel.
+ * This is scattered-data interpolation by a hierarchical ("pull-push") fill: a pixel that has a match keeps it, a pixel
+ * without one takes the mean of the matches in the smallest aligned block around it that holds enough of them.  The
+ * reference's product is such an image (disparity.png) and the GPC paper hands its matches to an interpolator; the rule
+ * here is this library's own, made of integers only, so that every implementation of it gives the same bytes.  The outputs
+ * of the consensus filter (whole d), of the refinement (d_ref) and of the pyramid merge (finer records first) are taken
+ * unchanged.
+ *
+ * Input: P = npairs lists rec[t][0 .. m_t), m_t = min(max(counts[t], 0), cap_per_pair), for images of width x height;
+ *   optionally one gpc_refinement ref[t][i] per record, as gpc_hip_refine_* writes it.
+ *   Source and target as in the consensus filter: (src_x, src_y) -> (tar_x, tar_y) of a correspondence; (x, y) ->
+ *     (x - (int)d, y) of a support.
+ *   A record PARTICIPATES iff source and target lie in [0, width) x [0, height); a support must also have d finite,
+ *     d == truncf(d) and |d| < 2^24; and, when ref is given and max_cost < 0xFFFF, flags bit 0 is set and cost <= max_cost.
+ *     With max_cost == 0xFFFF a record that was not evaluated still participates, with shift 0.
+ *   Value in 1/256 pixel (Q8): a support has one channel, 256 * (int)d - dx_q8; a correspondence two, u = 256 * (tar_x -
+ *     src_x) + dx_q8 and v = 256 * (tar_y - src_y) + dy_q8.  The shift is 0 without ref or when flags bit 0 is clear.  (A
+ *     support's value / 256 is the d that gpc_hip_refine_supports_device writes to its `out`.)
+ * Level 0: a pixel is OCCUPIED iff some participating record has it as its source; of several, the one with the lowest
+ *   input index stands for it (after a pyramid merge or a group union the finer or earlier record wins).  An occupied pixel
+ *   has its record's value and level 0.
+ * Pull: for l >= 1, cell (X, Y) of level l is the pixel block [X << l, (X + 1) << l) x [Y << l, (Y + 1) << l), clipped to
+ *   the image; n_l is the number of occupied pixels in it, S_l the exact integer sum of their values, per channel.  The grid
+ *   of level l has ((width - 1) >> l) + 1 columns and ((height - 1) >> l) + 1 rows; Lmax is the first level of one cell.
+ * Push: for a pixel (x, y) that is not occupied, l = 1, 2, .. min(max_level, Lmax) in turn: N and SUM are n_l and S_l
+ *   summed over the cells of the level-l grid within Chebyshev distance `spread` (0 or 1) of the pixel's cell (x >> l,
+ *   y >> l).  At the first l with N >= min_count the pixel's value is sgn(SUM) * ((2 |SUM| + N) div (2 N)) per channel -- the
+ *   mean, rounded half away from zero as the refinement rounds -- and its level is l.  If no level qualifies the value is
+ *   GPC_DENSE_NONE in every channel and the level 255.
+ * Output: value[P][C][height][width] int32 with C = 1 for supports and 2 for correspondences (the u plane, then the v
+ *   plane); level[P][height][width] uint8 (optional).  Every pixel of every pair is written.
+ * GPC_E_INVALID: a parameter out of range, a null required pointer, npairs < 1, cap_per_pair < 1, width or height < 1,
+ * max_cost < 0xFFFF without ref.  GPC_E_UNSUPPORTED: width or height > 32768 (what keeps |value| < 2^24 and every sum below
+ * 2^54), width * height > 2^30, npairs > 65535, npairs * cap_per_pair > 2^31 - 1. */
+#define GPC_DENSE_NONE (-2147483647 - 1) /* INT32_MIN: no block around the pixel holds min_count matches */
+typedef struct gpc_densify {
+  int32_t max_level;  /* 1 .. 15; levels above Lmax are never reached            */
+  int32_t min_count;  /* 1 .. 65536 matches a block needs before it fills a pixel */
+  int32_t spread;     /* 0: the pixel's own cell; 1: its 3x3 cells               */
+  int32_t max_cost;   /* 0 .. 0xFFFF; 0xFFFF = no ceiling; needs ref otherwise   */
+} gpc_densify;        /* documented defaults: 15, 1, 1, 0xFFFF */
+/* Records already on the device, in the layout the matchers write: d_rec and d_ref (which may be NULL) [npairs][cap_per_pair],
+ * d_counts[npairs] (read on the device), d_value[npairs][C][height][width], d_level[npairs][height][width] (may be NULL).
+ * Pure functions of their arguments: no forest is needed, and the calls only queue work on the context's stream (a memset,
+ * claim, pull, the levels above a 32 x 32 tile, push); read the outputs after gpc_hip_synchronize or another wait on the
+ * stream.  Workspaces of the context, grown on demand, per pixel and pair: 4 bytes (the owner plane) and at most
+ * (4 + 8 C) / 3 + 1 bytes (the cells' counts and sums: a third of a pixel's worth of cells over all levels). */
+int gpc_hip_densify_supports_device(gpc_hip_ctx* ctx, const gpc_support* d_rec, int cap_per_pair, const int32_t* d_counts,
+                                    const gpc_refinement* d_ref, int width, int height, int npairs, const gpc_densify* prm,
+                                    int32_t* d_value, uint8_t* d_level);
+int gpc_hip_densify_correspondences_device(gpc_hip_ctx* ctx, const gpc_correspondence* d_rec, int cap_per_pair,
+                                           const int32_t* d_counts, const gpc_refinement* d_ref, int width, int height, int npairs,
+                                           const gpc_densify* prm, int32_t* d_value, uint8_t* d_level);
+/* Match, refine and fill: gpc_hip_match_batch_device / gpc_hip_match_sequence_device exactly as they are, into the workspace
+ * of the context that holds every record of every pair (the one gpc_hip_consensus_batch_device uses); then, when
+ * refine_radius >= 1 (0 .. 6, 0 = none), the refinement of gpc_hip_refine_*_device over the raw images into a workspace of 8
+ * bytes per record slot; then the fill, with those refinements as ref.  Settings, refusals, statuses and waiting are those
+ * of the match they wrap; with two lanes (gpc_hip_set_pipeline(ctx, 2)) the lanes are drained and the call runs on the
+ * context's stream.  d_counts[P] (optional) receives the match's counts, d_ncand (optional) the candidate counts as the
+ * match writes them ([P][2] for the batch, [nframes] for the sequence).  Group mode: the batch form fills from the union;
+ * the sequence form is GPC_E_UNSUPPORTED, as the sequence itself.  max_cost < 0xFFFF with refine_radius 0: GPC_E_INVALID. */
+int gpc_hip_densify_batch_device(gpc_hip_ctx* ctx, const uint8_t* d_rawL, const uint8_t* d_rawR, int width, int height,
+                                 int npairs, const gpc_settings* settings, int refine_radius, const gpc_densify* prm,
+                                 int32_t* d_value, uint8_t* d_level, int32_t* d_counts, int32_t* d_ncand);
+int gpc_hip_densify_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int width, int height, int nframes,
+                                    const gpc_settings* settings, int refine_radius, const gpc_densify* prm, int32_t* d_value,
+                                    uint8_t* d_level, int32_t* d_counts, int32_t* d_ncand);
+/* Host records, counts, refinements and outputs through the records forms; synchronous, in chunks of at most 16 pairs,
+ * pageable arrays through the context's page-locked arena.  Each pair's first m_t records (and refinements) travel; what
+ * comes back equals the device forms byte for byte. */
+int gpc_hip_densify_supports(gpc_hip_ctx* ctx, const gpc_support* rec, int cap_per_pair, const int32_t* counts,
+                             const gpc_refinement* ref, int width, int height, int npairs, const gpc_densify* prm,
+                             int32_t* value, uint8_t* level);
+int gpc_hip_densify_correspondences(gpc_hip_ctx* ctx, const gpc_correspondence* rec, int cap_per_pair, const int32_t* counts,
+                                    const gpc_refinement* ref, int width, int height, int npairs, const gpc_densify* prm,
+                                    int32_t* value, uint8_t* level);
+
 /* ---- measurement -------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the context's stream.  When enabled every launch of
  * the named kernels is bracketed by hipEvents; gpc_hip_kernel_time returns the summed
@@ -880,7 +958,7 @@ int gpc_hip_enable_kernel_timing(gpc_hip_ctx* ctx, int enable);
 /* Restrict the bracketing to the kernels whose index bit is set (default: all).  Every pair of
  * event records costs a little stream time, so a benchmark times only the kernel it reports.  The mask has 32 bits and
  * gpc_hip_kernel_count() is the number of slots it addresses (at most 32).  gpc_hip_kernel_slots() counts every slot:
- * those from gpc_hip_kernel_count() on (k_refine, k_pyr_*) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
+ * those from gpc_hip_kernel_count() on (k_refine, k_pyr_*, k_dense_*) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
  * gpc_hip_kernel_launch_name and gpc_hip_kernel_time take their indices like any other. */
 int gpc_hip_set_kernel_timing_mask(gpc_hip_ctx* ctx, unsigned mask);
 int gpc_hip_reset_kernel_timing(gpc_hip_ctx* ctx);

@@ -68,6 +68,17 @@ class Consensus(C.Structure):
         super().__init__(int(cell), int(shifts), int(alpha_num), int(alpha_den))
 
 
+DENSE_NONE = -2 ** 31   # GPC_DENSE_NONE: no block around the pixel holds min_count matches (its level is 255)
+
+
+class Densify(C.Structure):
+    """gpc_densify: the parameters of the hierarchical fill (gpc_hip_densify_*); the documented defaults."""
+    _fields_ = [("max_level", C.c_int32), ("min_count", C.c_int32), ("spread", C.c_int32), ("max_cost", C.c_int32)]
+
+    def __init__(self, max_level=15, min_count=1, spread=1, max_cost=0xFFFF):
+        super().__init__(int(max_level), int(min_count), int(spread), int(max_cost))
+
+
 class FilterMask(C.Structure):
     """gpc::inference::Forest::FilterMask (reference inference.hpp:137-156)."""
     _fields_ = [
@@ -121,6 +132,8 @@ SYMBOLS = [
     "gpc_hip_pyramid_levels", "gpc_hip_pyramid_down_device", "gpc_hip_pyramid_merge_supports_device",
     "gpc_hip_pyramid_merge_correspondences_device", "gpc_hip_pyramid_batch_device", "gpc_hip_pyramid_sequence_device",
     "gpc_hip_pyramid_batch", "gpc_hip_pyramid_sequence",
+    "gpc_hip_densify_supports_device", "gpc_hip_densify_correspondences_device", "gpc_hip_densify_batch_device",
+    "gpc_hip_densify_sequence_device", "gpc_hip_densify_supports", "gpc_hip_densify_correspondences",
 ]
 
 
@@ -242,6 +255,15 @@ def load():
     L.gpc_hip_pyramid_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Settings),
                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gpc_hip_pyramid_sequence.argtypes = L.gpc_hip_pyramid_sequence_device.argtypes
+    L.gpc_hip_densify_supports_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(Densify), C.c_void_p, C.c_void_p]
+    L.gpc_hip_densify_correspondences_device.argtypes = L.gpc_hip_densify_supports_device.argtypes
+    L.gpc_hip_densify_supports.argtypes = L.gpc_hip_densify_supports_device.argtypes
+    L.gpc_hip_densify_correspondences.argtypes = L.gpc_hip_densify_supports_device.argtypes
+    L.gpc_hip_densify_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings),
+                                               C.c_int, C.POINTER(Densify), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_densify_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
+                                                  C.POINTER(Densify), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gpc_hip_match_batch_device_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(Settings), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                     C.c_void_p]
@@ -1075,6 +1097,59 @@ class Context:
                                              _ptr(counts), _ptr(lc), _ptr(ncand))
         self._ck(st, allow=(E_CAPACITY,))
         return out, counts, lc, ncand, st
+
+    # ---- dense maps from sparse matches (gpc_hip_densify_*): the hierarchical fill
+    def densify_records_device(self, d_rec, corr, cap_per_pair, d_counts, width, height, npairs, prm, d_value, d_level=0, d_ref=0):
+        """Records [npairs][cap_per_pair] already in HBM (corr: CORR_DTYPE, else SUPPORT_DTYPE), optionally their refinements
+        d_ref [npairs][cap_per_pair] of REFINEMENT_DTYPE -> d_value [npairs][C][height][width] int32 in 1/256 pixel (C = 2 for
+        correspondences, else 1; DENSE_NONE where nothing fills the pixel), d_level [npairs][height][width] uint8 (optional);
+        asynchronous, no forest needed.  Pointers are integers."""
+        fn = self.L.gpc_hip_densify_correspondences_device if corr else self.L.gpc_hip_densify_supports_device
+        self._ck(fn(self.h, C.c_void_p(d_rec), int(cap_per_pair), C.c_void_p(d_counts), C.c_void_p(d_ref or 0), int(width),
+                    int(height), int(npairs), C.byref(prm), C.c_void_p(d_value), C.c_void_p(d_level or 0)))
+
+    def densify_batch_device(self, d_rawL, d_rawR, width, height, npairs, settings, prm, d_value, d_level=0, refine_radius=0,
+                             d_counts=0, d_ncand=0):
+        """match_batch_device into the context's every-record workspace, the refinement over the raw images when
+        refine_radius >= 1, then the fill: d_value [npairs][1][height][width], d_level [npairs][height][width]."""
+        self._ck(self.L.gpc_hip_densify_batch_device(self.h, C.c_void_p(d_rawL), C.c_void_p(d_rawR), int(width), int(height),
+                                                     int(npairs), C.byref(settings), int(refine_radius), C.byref(prm),
+                                                     C.c_void_p(d_value), C.c_void_p(d_level or 0), C.c_void_p(d_counts or 0),
+                                                     C.c_void_p(d_ncand or 0)))
+
+    def densify_sequence_device(self, d_frames, width, height, nframes, settings, prm, d_value, d_level=0, refine_radius=0,
+                                d_counts=0, d_ncand=0):
+        """match_sequence_device, the refinement when refine_radius >= 1, then the fill: d_value [nframes-1][2][height][width]
+        (u plane, v plane), d_level [nframes-1][height][width]."""
+        self._ck(self.L.gpc_hip_densify_sequence_device(self.h, C.c_void_p(d_frames), int(width), int(height), int(nframes),
+                                                        C.byref(settings), int(refine_radius), C.byref(prm), C.c_void_p(d_value),
+                                                        C.c_void_p(d_level or 0), C.c_void_p(d_counts or 0),
+                                                        C.c_void_p(d_ncand or 0)))
+
+    def densify_records(self, records, counts, width, height, prm=None, ref=None, want_level=True):
+        """Host records [P, cap] (SUPPORT_DTYPE or CORR_DTYPE), their true counts [P] and optionally their refinements
+        [P, cap] of REFINEMENT_DTYPE -> (value [P, C, height, width] int32, level [P, height, width] uint8 or None)."""
+        records = np.asarray(records)
+        if records.dtype not in (SUPPORT_DTYPE, CORR_DTYPE) or records.ndim != 2 or records.shape[1] < 1 or records.shape[0] < 1:
+            raise ValueError("records: [P, cap] of SUPPORT_DTYPE or CORR_DTYPE")
+        corr = records.dtype == CORR_DTYPE
+        if not records.flags.c_contiguous:
+            records = np.ascontiguousarray(records)
+        counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+        P, cap = records.shape
+        if len(counts) != P:
+            raise ValueError("counts: one per pair")
+        if ref is not None:
+            ref = np.ascontiguousarray(ref)
+            if ref.dtype != REFINEMENT_DTYPE or ref.shape != records.shape:
+                raise ValueError("ref: [P, cap] of REFINEMENT_DTYPE")
+        prm = prm if prm is not None else Densify()
+        width, height = int(width), int(height)
+        value = np.empty((P, 2 if corr else 1, max(height, 1), max(width, 1)), np.int32)
+        level = np.empty((P, max(height, 1), max(width, 1)), np.uint8) if want_level else None
+        fn = self.L.gpc_hip_densify_correspondences if corr else self.L.gpc_hip_densify_supports
+        self._ck(fn(self.h, _ptr(records), cap, _ptr(counts), _ptr(ref), width, height, P, C.byref(prm), _ptr(value), _ptr(level)))
+        return value, level
 
     # ---- fern training: the scoring loop
     def train_set(self, triplets):
