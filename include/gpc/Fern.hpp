@@ -231,6 +231,39 @@ class Fern {
     }
   }
 
+  // Extensions for Forest::trainAndExport over a device-resident set (gpc/training.hpp), which trains all ferns in one call:
+  // the two host halves of train() around it.  drawHyperplanes: what train() draws, in its order and from this fern's
+  // generator (dumped like train()'s); adoptTrained: the chosen parameters become the fern's, and the table train() prints.
+  std::vector<gpc_split> drawHyperplanes(OptimizerSettings optsetting) {
+    const int depth = fernsettings.maxDepth, nres = optsetting.numResamples_;
+    std::vector<gpc_split> cand((size_t)depth * (nres > 0 ? nres : 0));
+    SplitParams_t p;
+    for (int level = 0; level < depth; level++)
+      for (int k = 0; k < nres; k++) {
+        Feature.sampleHyperplane(fernsettings.scale, p);
+        cand[(size_t)level * nres + k] = toSplit(p);
+      }
+    if (const char* dump = std::getenv("GPC_TRAIN_DUMP_CANDIDATES")) {
+      std::ofstream f(dump, std::ios::app);
+      for (auto& c : cand) f << c.i << " " << c.j << "\n";
+    }
+    return cand;
+  }
+  void adoptTrained(const gpc_split* chosen, const gpc_split_stats* stats) {
+    fernparams.resize(fernsettings.maxDepth);
+    cout << setw(7) << "Level" << setw(10) << "Prec" << setw(10) << "Rec" << setw(10) << "Har" << setw(8) << "Tot"
+         << setw(8) << "TP" << setw(8) << "FP" << setw(8) << "FN" << setw(6) << "scale" << setw(5) << "tau"
+         << setw(5) << "i" << setw(5) << "j" << endl;
+    for (int level = 0; level < fernsettings.maxDepth; level++) {
+      fernparams[level] = fromSplit(chosen[level]);
+      cout << setw(7) << level << setw(10) << stats[level].prec << setw(10) << stats[level].rec << setw(10)
+           << stats[level].hmean << setw(8) << stats[level].tot << setw(8) << stats[level].tp << setw(8)
+           << stats[level].fp << setw(8) << stats[level].fn << setw(6) << fernsettings.scale << setw(5)
+           << fernparams[level].tau << setw(5) << fernparams[level].i << setw(5) << fernparams[level].j << endl;
+    }
+  }
+  int getMaxDepth() { return fernsettings.maxDepth; }
+
   std::vector<SplitParams_t> getParameters() { return fernparams; }
   int getScale() { return fernsettings.scale; }
 };  // Fern

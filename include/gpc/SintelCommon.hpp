@@ -7,7 +7,8 @@
 //   - seed(s): frame ordinal f draws from std::mt19937(s + f), the final shuffle runs after srand(s);
 //   - a cap of 1000 x numTripletsPerPair sampler draws per frame (the reference loops forever on a frame without a
 //     valid pixel);
-//   - extractTrainingSet(): the extracted set stays on the device (DeviceTrainingSet) instead of becoming host objects.
+//   - extractTrainingSet(): the extracted set stays on the device (DeviceTrainingSet) instead of becoming host objects;
+//   - DeviceTrainingSet::fromHost / fromBytes: a host set uploaded once, for Forest::trainAndExport's device overload.
 #ifndef _GPC_SintelCommon
 #define _GPC_SintelCommon
 
@@ -56,6 +57,31 @@ class DeviceTrainingSet {
   gpc_hip_train_set* set() const { return set_; }
   // triplets [first, first + n) in the byte order of Feature::storeAllTriplets (n * 3 * 729 bytes)
   int read(int first, int n, uint8_t* aos) const { return set_ ? gpc_hip_train_set_read(ctx_, set_, first, n, aos) : (n ? GPC_E_INVALID : GPC_OK); }
+
+  // n triplets in the byte order of Feature::storeAllTriplets (a loaded .bin as it is) as a device set of this thread's
+  // context: one upload, all marks cleared.  Empty on failure (gpc::inference::lastStatus() says why).
+  static DeviceTrainingSet fromBytes(const uint8_t* aos, int n) {
+    if (!aos || n <= 0) return DeviceTrainingSet();
+    gpc_hip_ctx* ctx = gpc::inference::detail::holder().ctx;
+    if (!ctx) return DeviceTrainingSet();
+    gpc_hip_train_set* set = nullptr;
+    const int st = gpc_hip_train_set_create(ctx, aos, n, &set);
+    if (st != GPC_OK) {
+      gpc::inference::detail::fail(st, ctx, "gpc_hip_train_set_create");
+      return DeviceTrainingSet();
+    }
+    return DeviceTrainingSet(ctx, set, n);
+  }
+  // the same from the reference's host vector (what loadTrainingData returns); the triplets' split marks are not carried over
+  static DeviceTrainingSet fromHost(std::vector<GPCTriplet_t>& data) {
+    std::vector<uint8_t> aos(data.size() * 3 * 729);
+    for (size_t k = 0; k < data.size(); ++k) {
+      std::memcpy(&aos[(k * 3 + 0) * 729], data[k].ref.feature.data(), 729);
+      std::memcpy(&aos[(k * 3 + 1) * 729], data[k].pos.feature.data(), 729);
+      std::memcpy(&aos[(k * 3 + 2) * 729], data[k].neg.feature.data(), 729);
+    }
+    return fromBytes(aos.data(), (int)data.size());
+  }
 
  private:
   void swap(DeviceTrainingSet& o) {

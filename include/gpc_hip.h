@@ -390,6 +390,28 @@ int gpc_hip_train_begin_fern(gpc_hip_ctx* ctx, gpc_hip_train_set* set, int reset
 int gpc_hip_train_eval_level(gpc_hip_ctx* ctx, gpc_hip_train_set* set, const gpc_split* cand, int ncand,
                              int taulo, int tauhi, int32_t* tp, int32_t* fp, int32_t* tot);
 int gpc_hip_train_commit_level(gpc_hip_ctx* ctx, gpc_hip_train_set* set, const gpc_split* best, int mark_split);
+/* Forest::trainAndExport's loop over the ferns (training.hpp:113-135) over ONE resident set, without a copy of any triplet:
+ *   cand    [nferns][max_depth][num_resamples]: cand[(f * max_depth + level) * num_resamples + k] is fern f's k-th draw of
+ *           sampleHyperplane at `level` (its tau is ignored, as in gpc_hip_train_fern);
+ *   draws   [nferns][draws_per_fern]: draws[f * draws_per_fern + d] is the index into `set` of fern f's d-th bootstrap draw
+ *           (repeats are the point; draws_per_fern may exceed the set's size).  NULL: every fern trains on the whole set,
+ *           each triplet once;
+ *   fernparams, level_stats   [nferns][max_depth].
+ * Fern f's output is exactly what gpc_hip_train_fern returns for a training set that holds the triplets set[draws[f][0]],
+ * set[draws[f][1]], ... with all marks cleared -- what trainAndExport + Fern::train compute on their subSample: tp, fp, fn
+ * and tot are sums over the draws, a triplet drawn m times counts m times.  The set's own marks are neither read nor
+ * changed (the reference's bootstraps are copies it throws away).  On the device a bootstrap is one byte of multiplicity
+ * and one byte of flags per triplet and fern; all ferns advance level by level in the same launches, in groups where
+ * nferns * num_resamples or the workspaces ask for it, and the host reads one block of counts per level and group.
+ * GPC_E_INVALID, before anything is launched: null pointers (draws excepted), nferns <= 0, max_depth <= 0, num_resamples < 0,
+ * draws_per_fern <= 0 with draws, a draw outside [0, size), a hyperplane outside the patch.  GPC_E_UNSUPPORTED, before
+ * anything is launched: max_depth > 64, tauhi - taulo > 64, num_resamples > 65535, and a fern that draws one triplet more
+ * than 255 times (up to 255 the counts are exact; no count ever wraps).  With num_resamples == 0 or tauhi <= taulo nothing
+ * is evaluated and the outputs are zeros, as Fern::train leaves them.  Every workspace is released before the call returns.
+ * Synchronous. */
+int gpc_hip_train_forest(gpc_hip_ctx* ctx, gpc_hip_train_set* set, int nferns, int max_depth, const gpc_split* cand,
+                         int num_resamples, int taulo, int tauhi, int only_score_non_split, double w1,
+                         const int32_t* draws, int draws_per_fern, gpc_split* fernparams, gpc_split_stats* level_stats);
 
 /* ---- training-set extraction ---------------------------------------------------- */
 /* One triplet of keypoints: the reference point in the LEFT frame, the positive and the negative point in the RIGHT

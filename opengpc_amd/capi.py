@@ -115,7 +115,7 @@ SYMBOLS = [
     "gpc_hip_kernel_name", "gpc_hip_kernel_launch_name", "gpc_hip_kernel_time",
     "gpc_hip_train_set_create", "gpc_hip_train_set_destroy", "gpc_hip_train_set_size", "gpc_hip_train_set_marks",
     "gpc_hip_train_eval_split", "gpc_hip_train_mark_split_samples", "gpc_hip_train_fern",
-    "gpc_hip_train_begin_fern", "gpc_hip_train_eval_level", "gpc_hip_train_commit_level",
+    "gpc_hip_train_begin_fern", "gpc_hip_train_eval_level", "gpc_hip_train_commit_level", "gpc_hip_train_forest",
     "gpc_hip_extract_triplets", "gpc_hip_extract_triplets_device", "gpc_hip_train_set_read",
     "gpc_hip_match_sequence_device", "gpc_hip_match_sequence",
     "gpc_hip_score_supports_device", "gpc_hip_score_correspondences_device", "gpc_hip_score_batch_device",
@@ -292,6 +292,7 @@ def load():
     L.gpc_hip_train_begin_fern.argtypes = [vp, vp, ci]
     L.gpc_hip_train_eval_level.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
     L.gpc_hip_train_commit_level.argtypes = [vp, vp, vp, ci]
+    L.gpc_hip_train_forest.argtypes = [vp, vp, ci, ci, vp, ci, ci, ci, ci, C.c_double, vp, ci, vp, vp]
     L.gpc_hip_extract_triplets.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
     L.gpc_hip_extract_triplets_device.argtypes = L.gpc_hip_extract_triplets.argtypes
     L.gpc_hip_train_set_read.argtypes = [vp, vp, ci, ci, vp]
@@ -1373,6 +1374,28 @@ class TrainSet:
         self.ctx._ck(self.ctx.L.gpc_hip_train_fern(self.ctx.h, self.h, int(max_depth), _ptr(c), int(num_resamples),
                                                    int(taulo), int(tauhi), int(bool(only_score_non_split)),
                                                    C.c_double(w1), _ptr(fp), _ptr(st)))
+        return fp, st
+
+    def train_forest(self, nferns, max_depth, cand, num_resamples, taulo, tauhi, only_score_non_split, w1, draws=None):
+        """Every fern of a forest over this one resident set (gpc_hip_train_forest).  cand[f, level, k] = fern f's k-th
+        hyperplane sample of `level`; draws[f, d] = index into the set of fern f's d-th bootstrap draw (None: every fern
+        trains on the whole set).  Returns (params[nferns, max_depth], stats[nferns, max_depth]); the set's marks stay."""
+        c = np.ascontiguousarray(cand, SPLIT_DTYPE).reshape(-1)
+        if len(c) < nferns * max_depth * num_resamples:
+            raise ValueError("need nferns * max_depth * num_resamples hyperplane samples")
+        d, per_fern = None, 0
+        if draws is not None:
+            d = np.ascontiguousarray(draws, np.int32)
+            if d.ndim != 2 or d.shape[0] != nferns:
+                raise ValueError("draws must have shape (nferns, draws_per_fern)")
+            per_fern = d.shape[1]
+        shape = (max(nferns, 0), max(max_depth, 0))
+        fp = np.zeros(shape, SPLIT_DTYPE)
+        st = np.zeros(shape, STATS_DTYPE)
+        self.ctx._ck(self.ctx.L.gpc_hip_train_forest(self.ctx.h, self.h, int(nferns), int(max_depth), _ptr(c),
+                                                     int(num_resamples), int(taulo), int(tauhi),
+                                                     int(bool(only_score_non_split)), C.c_double(w1), _ptr(d), per_fern,
+                                                     _ptr(fp), _ptr(st)))
         return fp, st
 
     def begin_fern(self, reset_marks):

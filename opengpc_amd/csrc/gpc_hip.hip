@@ -47,6 +47,7 @@
 #include "k_track.h"
 #include "k_track_stream.h"
 #include "k_train.h"
+#include "k_train_forest.h"
 #include "k_union.h"
 #include "owners.h"
 #include "pyramid_host.h"
@@ -96,6 +97,10 @@ enum KernelId {
   KID_DENSE_PULL,
   KID_DENSE_TOP,
   KID_DENSE_PUSH,
+  KID_TF_BEGIN,
+  KID_TF_EVAL,
+  KID_TF_TOT,
+  KID_TF_COMMIT,
   KID_COUNT
 };
 const char* const kKernelNames[KID_COUNT] = {
@@ -105,7 +110,8 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_cons_cells", "k_cons_scan", "k_cons_scatter", "k_cons_count", "k_cons_blocks", "k_cons_write",
     "k_trs_fill", "k_trs_scatter", "k_trs_link", "k_trs_settle", "k_trs_scan", "k_trs_walk", "k_trs_save", "k_trs_ncand",
     "k_score_records", "k_score_matchable", "k_refine", "k_pyr_down", "k_pyr_keep", "k_pyr_scan", "k_pyr_write",
-    "k_dense_claim", "k_dense_pull", "k_dense_top", "k_dense_push"};
+    "k_dense_claim", "k_dense_pull", "k_dense_top", "k_dense_push",
+    "k_tf_begin", "k_tf_eval", "k_tf_tot", "k_tf_commit"};
 
 // The owners of owners.h over the HIP runtime.  Everything the library allocates passes through these four backends, which
 // also keep the process-wide counts that gpc_hip_debug_live_resources reports.
@@ -420,6 +426,7 @@ struct gpc_hip_ctx {
   // (allocated by the call, released before it returns)
   DevBuf ext_raw, ext_smooth, ext_grad, ext_groups;
   int extract_frames = 0;     // GPC_HIP_EXTRACT_FRAMES: frame pairs per chunk (tests; default: 64 MiB of smoothed frames)
+  int train_group = 0;        // GPC_HIP_TRAIN_GROUP: ferns per group of gpc_hip_train_forest (tests; default: what grid and workspace allow)
   int seq_frames = 0;         // GPC_HIP_SEQ_FRAMES: frames per chunk of gpc_hip_match_sequence (tests; default 16)
 
   // Forest::preprocessImage -> Forest::rectifiedMatch without the round trip (the reference's PreprocessedImage travels by
@@ -2271,6 +2278,10 @@ int gpc_hip_create(int device, gpc_hip_ctx** out) {
   if (const char* e = getenv("GPC_HIP_EXTRACT_FRAMES")) {
     const int v = atoi(e);
     if (v >= 1) c->extract_frames = v;
+  }
+  if (const char* e = getenv("GPC_HIP_TRAIN_GROUP")) {
+    const int v = atoi(e);
+    if (v >= 1) c->train_group = v;
   }
   c->debug = getenv("GPC_HIP_DEBUG") != nullptr;
   c->debug_plan = getenv("GPC_HIP_DEBUG_PLAN") != nullptr;
@@ -5556,6 +5567,26 @@ int train_scratch(gpc_hip_ctx* c, gpc_hip_train_set* t, size_t ncounts, size_t n
 
 bool split_ok(const gpc_split& p) { return p.i >= 0 && p.i < TS_PATCH && p.j >= 0 && p.j < TS_PATCH; }
 
+// The candidate loop of Fern::train for one level (Fern.hpp:336-352) over counts already taken: tp / fp [num_resamples][ntau],
+// `tot` samples counted.  *best and *stats carry over from the level before: a level on which nothing scores above 0 keeps
+// the previous winner (:352), and the statistics are those of the last candidate evaluated (:357).
+void select_level(const gpc_split* cand, int num_resamples, int taulo, int ntau, const int32_t* tp, const int32_t* fp,
+                  int32_t tot, double w1, gpc_split* best, gpc_split_stats* stats) {
+  float max_score = 0.f;
+  for (int k = 0; k < num_resamples; ++k) {
+    gpc_split p = cand[k];                                                  // sampleHyperplane          :339
+    for (int q = 0; q < ntau; ++q) {
+      p.tau = taulo + q;
+      const int a = tp[(size_t)k * ntau + q], b = fp[(size_t)k * ntau + q];
+      split_stats(a, b, tot - a - b, tot, w1, stats);                      // evalSplit                  :343
+      if (stats->hmean > max_score) {                                       // double against float       :346
+        *best = p;
+        max_score = (float)stats->hmean;
+      }
+    }
+  }
+}
+
 }  // namespace
 
 int gpc_hip_train_set_create(gpc_hip_ctx* c, const uint8_t* triplets, int n, gpc_hip_train_set** out) {
@@ -5722,26 +5753,167 @@ int gpc_hip_train_fern(gpc_hip_ctx* c, gpc_hip_train_set* t, int max_depth, cons
   for (int l = 0; l < max_depth; ++l) fernparams[l] = gpc_split{0, 0, 0};  // fernparams.resize(maxDepth)  :318
   CHK(gpc_hip_train_begin_fern(c, t, only_score_non_split));                // resetMarkOnSamples        :333
   for (int level = 0; level < max_depth; ++level) {
-    float max_score = 0.f;
     int32_t tot = 0;
     if (num_resamples > 0 && ntau > 0)
       CHK(gpc_hip_train_eval_level(c, t, cand + (size_t)level * num_resamples, num_resamples, taulo, tauhi, tp.data(),
                                    fp.data(), &tot));
-    for (int k = 0; k < num_resamples; ++k) {
-      fernparams[level] = cand[(size_t)level * num_resamples + k];          // sampleHyperplane          :339
-      for (int q = 0; q < ntau; ++q) {
-        fernparams[level].tau = taulo + q;
-        const int a = tp[(size_t)k * ntau + q], b = fp[(size_t)k * ntau + q];
-        split_stats(a, b, tot - a - b, tot, w1, &stats);                   // evalSplit                  :343
-        if (stats.hmean > max_score) {                                      // double against float       :346
-          best = fernparams[level];
-          max_score = (float)stats.hmean;
-        }
-      }
-    }
+    select_level(cand + (size_t)level * num_resamples, num_resamples, taulo, ntau, tp.data(), fp.data(), tot, w1, &best,
+                 &stats);
     fernparams[level] = best;                                               // :352 (also when nothing scored above 0)
     CHK(gpc_hip_train_commit_level(c, t, &best, only_score_non_split));     // markSplitSamples(level)    :355
     level_stats[level] = stats;                                             // what train() prints        :357
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GPC_OK;
+}
+
+// Forest::trainAndExport's loop over the ferns (training.hpp:113-135) without its copies: every fern's bootstrap is a
+// multiplicity per triplet of the ONE resident set, and the ferns of a group advance level by level in the same launches
+// (k_train_forest.h).  Per level the host reads the group's counts once, runs the reference's selection (select_level, as
+// gpc_hip_train_fern does) and sends the winners back.  The per-fern state, the staging block and every other workspace
+// are owners local to the call: released when it returns, whichever way.
+int gpc_hip_train_forest(gpc_hip_ctx* c, gpc_hip_train_set* t, int nferns, int max_depth, const gpc_split* cand,
+                         int num_resamples, int taulo, int tauhi, int only_score_non_split, double w1, const int32_t* draws,
+                         int draws_per_fern, gpc_split* fernparams, gpc_split_stats* level_stats) {
+  CHK(train_check(c, t));
+  if (nferns <= 0 || max_depth <= 0 || !cand || num_resamples < 0 || !fernparams || !level_stats ||
+      (draws && draws_per_fern <= 0))
+    return GPC_E_INVALID;
+  // (a fern's candidates of one level are one grid dimension)
+  if (max_depth > 64 || tauhi - taulo > TS_MAXTAU || num_resamples > 65535) return GPC_E_UNSUPPORTED;
+  const int ntau = tauhi > taulo ? tauhi - taulo : 0;
+  const size_t per_fern = (size_t)max_depth * num_resamples;  // hyperplanes of one fern
+  for (size_t k = 0; k < (size_t)nferns * per_fern; ++k)
+    if (!split_ok(cand[k])) return GPC_E_INVALID;
+  if (draws)
+    for (size_t k = 0; k < (size_t)nferns * draws_per_fern; ++k)
+      if (draws[k] < 0 || draws[k] >= t->n) return GPC_E_INVALID;
+  for (size_t k = 0; k < (size_t)nferns * max_depth; ++k) fernparams[k] = gpc_split{0, 0, 0};  // fernparams.resize(maxDepth)
+  memset(level_stats, 0, sizeof(gpc_split_stats) * (size_t)nferns * max_depth);
+  if (num_resamples == 0 || ntau == 0) return GPC_OK;  // nothing is evaluated: Fern::train leaves zeros (Fern.hpp:316-357)
+
+  const int n = t->n;
+  const long np = t->np;
+  // fern f's multiplicities m[np] and one past its last drawn triplet, rounded up to a lane's 4; false: more than 255 copies
+  auto count = [&](int f, uint8_t* m, int32_t* lim) -> bool {
+    if (!draws) {
+      memset(m, 1, (size_t)n);
+      memset(m + n, 0, (size_t)(np - n));
+      *lim = (n + 3) & ~3;
+      return true;
+    }
+    memset(m, 0, (size_t)np);
+    const int32_t* d = draws + (size_t)f * draws_per_fern;
+    int32_t hi = 0;
+    for (int k = 0; k < draws_per_fern; ++k) {
+      if (m[d[k]] == 255) return false;
+      ++m[d[k]];
+      if (d[k] > hi) hi = d[k];
+    }
+    *lim = (hi + 4) & ~3;
+    return true;
+  };
+  auto too_many = [&]() {
+    snprintf(c->err, sizeof(c->err), "gpc_hip_train_forest: one fern draws a triplet more than 255 times");
+    return GPC_E_UNSUPPORTED;
+  };
+
+  // ferns per group: (fern, candidate) is one grid dimension; 1 GiB of flags and multiplicities, 256 MiB of counters at most
+  const size_t nc = (size_t)num_resamples * ntau;
+  size_t G = (size_t)nferns;
+  G = std::min(G, (size_t)65535 / num_resamples);
+  G = std::min(G, std::max<size_t>(1, ((size_t)1 << 29) / (size_t)np));
+  G = std::min(G, std::max<size_t>(1, ((size_t)1 << 26) / (2 * nc + 1)));
+  if (c->train_group > 0) G = std::min(G, (size_t)c->train_group);
+  if (draws && G < (size_t)nferns) {  // several groups: nothing is launched before every fern's multiplicities are known to fit
+    std::vector<uint8_t> m((size_t)np);
+    int32_t lim;
+    for (int f = 0; f < nferns; ++f)
+      if (!count(f, m.data(), &lim)) return too_many();
+  }
+
+  // page-locked staging: [multiplicities G x np | hyperplanes G x per_fern | winners G | lim G | counters G x (2 nc + 1)]
+  const size_t ncounts = G * (2 * nc + 1);
+  const size_t o_cand = G * (size_t)np, o_best = o_cand + sizeof(gpc_split) * G * per_fern, o_lim = o_best + sizeof(gpc_split) * G,
+               o_cnt = o_lim + sizeof(int32_t) * G;
+  Pinned<uint8_t> h_mem;
+  DevBlock<uint8_t> d_flags, d_mult;
+  DevBlock<gpc::GpcSplit> d_cand;  // the group's hyperplanes of every level, then its winners of the current one
+  DevBlock<int32_t> d_cnt;         // counters of the current level [tp | fp | tot], then lim
+  HIPCHK(c, h_mem.alloc(o_cnt + sizeof(int32_t) * ncounts, hipHostMallocDefault));
+  HIPCHK(c, d_flags.alloc(G * (size_t)np));
+  HIPCHK(c, d_mult.alloc(G * (size_t)np));
+  HIPCHK(c, d_cand.alloc(sizeof(gpc_split) * (G * per_fern + G)));
+  HIPCHK(c, d_cnt.alloc(sizeof(int32_t) * (ncounts + G)));
+  uint8_t* h_mult = h_mem.p;
+  gpc_split* h_cand = reinterpret_cast<gpc_split*>(h_mem.p + o_cand);
+  gpc_split* h_best = reinterpret_cast<gpc_split*>(h_mem.p + o_best);
+  int32_t* h_lim = reinterpret_cast<int32_t*>(h_mem.p + o_lim);
+  int32_t* h_cnt = reinterpret_cast<int32_t*>(h_mem.p + o_cnt);
+  gpc::GpcSplit* d_best = d_cand.p + G * per_fern;
+  int32_t* d_lim = d_cnt.p + ncounts;
+  std::vector<gpc_split> best(G);
+  std::vector<gpc_split_stats> stats(G);
+
+  for (int f0 = 0; f0 < nferns; f0 += (int)G) {
+    const int g = std::min((int)G, nferns - f0);
+    long span = 0;  // triplets any fern of the group reads
+    for (int f = 0; f < g; ++f) {
+      if (!count(f0 + f, h_mult + (size_t)f * np, &h_lim[f])) return too_many();  // (one group: nothing launched yet)
+      span = std::max(span, (long)h_lim[f]);
+    }
+    memcpy(h_cand, cand + (size_t)f0 * per_fern, sizeof(gpc_split) * g * per_fern);
+    HIPCHK(c, hipMemcpyAsync(d_mult.p, h_mult, (size_t)g * np, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_cand.p, h_cand, sizeof(gpc_split) * g * per_fern, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_lim, h_lim, sizeof(int32_t) * g, hipMemcpyHostToDevice, c->stream));
+    {
+      Timed tm(c, KID_TF_BEGIN);
+      hipLaunchKernelGGL(gpc::k_tf_begin, dim3((unsigned)(np / TS_THREADS), g), dim3(TS_THREADS), 0, c->stream, d_flags.p, n, np);
+    }
+    for (int f = 0; f < g; ++f) {
+      best[f] = gpc_split{0, 0, 0};                     // SplitParams_t bestParams;            Fern.hpp:316
+      memset(&stats[f], 0, sizeof(gpc_split_stats));
+    }
+    const size_t gnc = (size_t)g * nc, gcounts = 2 * gnc + g;
+    // chunk length as in gpc_hip_train_eval_level: the longest that still leaves >= 4096 workgroups
+    int iters = 64;
+    while (iters > 4 && ((span + (long)iters * TS_ITER - 1) / ((long)iters * TS_ITER)) * g * num_resamples < 4096) iters >>= 1;
+    const unsigned chunks = (unsigned)((span + (long)iters * TS_ITER - 1) / ((long)iters * TS_ITER));
+    for (int level = 0; level < max_depth; ++level) {
+      HIPCHK(c, hipMemsetAsync(d_cnt.p, 0, sizeof(int32_t) * gcounts, c->stream));
+      {
+        Timed tm(c, KID_TF_EVAL);
+        hipLaunchKernelGGL(gpc::k_tf_eval, dim3(chunks, (unsigned)(g * num_resamples)), dim3(TS_THREADS), 0, c->stream,
+                           (const uint8_t*)t->planes.p, (const uint8_t*)d_flags.p, (const uint8_t*)d_mult.p,
+                           (const int32_t*)d_lim, np, (const gpc::GpcSplit*)d_cand.p + (size_t)level * num_resamples,
+                           (int)per_fern, num_resamples, taulo, ntau, iters, d_cnt.p, d_cnt.p + gnc);
+      }
+      {
+        Timed tm(c, KID_TF_TOT);
+        hipLaunchKernelGGL(gpc::k_tf_tot, dim3((unsigned)std::min<long>((span / 4 + TS_THREADS - 1) / TS_THREADS, 32), g), dim3(TS_THREADS), 0,
+                           c->stream, (const uint8_t*)d_flags.p, (const uint8_t*)d_mult.p, (const int32_t*)d_lim, np,
+                           d_cnt.p + 2 * gnc);
+      }
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(h_cnt, d_cnt.p, sizeof(int32_t) * gcounts, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));  // the level's one read-back
+      for (int f = 0; f < g; ++f) {
+        select_level(h_cand + (size_t)f * per_fern + (size_t)level * num_resamples, num_resamples, taulo, ntau,
+                     h_cnt + (size_t)f * nc, h_cnt + gnc + (size_t)f * nc, h_cnt[2 * gnc + f], w1, &best[f], &stats[f]);
+        fernparams[(size_t)(f0 + f) * max_depth + level] = best[f];    // :352 (also when nothing scored above 0)
+        level_stats[(size_t)(f0 + f) * max_depth + level] = stats[f];  // what train() prints        :357
+        h_best[f] = best[f];
+      }
+      if (level + 1 == max_depth) break;  // (the marks of the bootstrap go with it: nothing reads the last level's)
+      HIPCHK(c, hipMemcpyAsync(d_best, h_best, sizeof(gpc_split) * g, hipMemcpyHostToDevice, c->stream));
+      {
+        Timed tm(c, KID_TF_COMMIT);
+        hipLaunchKernelGGL(gpc::k_tf_commit, dim3((unsigned)((span + TS_THREADS - 1) / TS_THREADS), g), dim3(TS_THREADS), 0,
+                           c->stream, (const uint8_t*)t->planes.p, d_flags.p, (const uint8_t*)d_mult.p, (const int32_t*)d_lim, np,
+                           (const gpc::GpcSplit*)d_best, only_score_non_split);
+      }
+      HIPCHK(c, hipGetLastError());
+    }
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return GPC_OK;

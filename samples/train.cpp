@@ -46,8 +46,13 @@ int main(int argc, char** argv) {
 
   gpc::datasource::SintelOpticalFlow source;
   std::cout << "Loading dataset" << std::endl;
-  std::vector<gpc::training::Feature::GPCPatchTriplet> data = source.loadTrainingData(dataset);
+  // the set goes to the device once and stays there: every fern's bootstrap is a multiplicity per triplet of it
+  gpc::datasource::DeviceTrainingSet device;
+  {
+    std::vector<gpc::training::Feature::GPCPatchTriplet> data = source.loadTrainingData(dataset);
+    device = gpc::datasource::DeviceTrainingSet::fromHost(data);
+  }
   gpc::training::Forest trainer;
-  trainer.trainAndExport(data, settings, optimizer, forest);
-  return data.empty() ? 1 : 0;
+  trainer.trainAndExport(device, settings, optimizer, forest);
+  return device.empty() ? 1 : 0;
 }
