@@ -53,6 +53,12 @@
 #include "pyramid_host.h"
 #include "track_stream_host.h"
 
+// Five sections of the host code below are cut out at their rules into files of their own, csrc/host_*.h, and included where
+// they stood: host_staging.h (what scoring, tracks and the stages after them share), host_consensus.h, host_refine.h,
+// host_pyramid.h and host_dense.h.  They are parts of THIS translation unit, not self-contained headers: each needs what
+// stands above its include, and `#pragma once` is all the guard it has.  Each says its linkage once: an anonymous namespace
+// with its types, helpers and templates, then one extern "C" block with its entry points.  Everything else is still here.
+
 namespace {
 
 enum KernelId {
@@ -798,6 +804,9 @@ bool next_int(const char*& p, int& v) {
 
 // ---------------------------------------------------------------- pipeline stages
 
+// The two device-wide matchers run_match hands over to stand below it and use this section's helpers.  They are declared
+// here, not moved in front of run_match: the order in which the translation unit first names the kernel templates is the
+// order of their instantiations in the device code, and run_match names the row joins first.
 // seq: the code images (and candidate bytes) are a frame sequence [npairs + 1][H][W], pair p = frames (p, p + 1); the
 // statistics are in the pair layout all the same (k_seq_stats)
 int run_global_match(gpc_hip_ctx* c, int W, int H, int npairs, const gpc_settings* s, int mode, const uint8_t* d_cand,
@@ -3391,6 +3400,13 @@ int gpc_hip_match_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, 
   return status;
 }
 
+}  // extern "C"
+
+// (a part of this translation unit: see the note below the includes at the top)
+#include "host_staging.h"
+
+extern "C" {
+
 // ------------------------------------------------------------------ scoring against ground truth
 
 static_assert(sizeof(gpc_score) == sizeof(gpc::ScoreDev), "gpc_score and the kernels' view of it");
@@ -3488,47 +3504,6 @@ int gpc_hip_score_correspondences_device(gpc_hip_ctx* c, const gpc_correspondenc
   return score_records_entry(c, d_corr, true, cap_per_pair, d_counts, W, H, npairs, truth, thr, n_thr, d_scores);
 }
 
-// Every record of every pair of a call, kept on the device: what match-and-score and match-and-filter work on.  A group has
-// at most one record per left candidate, a union at most G.
-namespace {
-struct AllRecords {
-  void* rec;        // [npairs][cap]: gpc_support of pairs, gpc_correspondence of frames
-  int32_t* counts;  // [npairs]
-  int cap;
-};
-// lanes = 1 for the duration of the match: it runs on the context itself
-struct StrictScope {
-  gpc_hip_ctx* c;
-  int lanes;
-  explicit StrictScope(gpc_hip_ctx* ctx) : c(ctx), lanes(ctx->pipeline) { c->pipeline = 1; }
-  ~StrictScope() { c->pipeline = lanes; }
-};
-}  // namespace
-
-// what the match itself refuses is refused here, and a capacity that does not fit an int, before any workspace is made
-static int all_records_cap(gpc_hip_ctx* c, const gpc_settings* s, int W, int H, bool seq, int* cap) {
-  CHK(match_usable(c, s, W, H, seq));
-  const long n = (long)(c->ngroups > 1 ? c->ngroups : 1) * (W - 2 * GPC_R) * (H - 2 * GPC_R) + 1;
-  if (n > 0x7FFFFFFFl) return GPC_E_UNSUPPORTED;
-  *cap = (int)n;
-  return GPC_OK;
-}
-
-// d_b null: d_a holds npairs + 1 frames; else d_a and d_b hold the left and right images of npairs pairs.  r->cap is what
-// all_records_cap gave for the call (filtering checks its own limits against it in between)
-static int all_records(gpc_hip_ctx* c, const uint8_t* d_a, const uint8_t* d_b, int W, int H, int npairs, const gpc_settings* s,
-                       int32_t* d_ncand, AllRecords* r) {
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->pipeline > 1) CHK(drain_lanes(c));
-  CHK(ensure(c, c->all_rec, (d_b ? sizeof(gpc_support) : sizeof(gpc_correspondence)) * (size_t)r->cap * npairs));
-  CHK(ensure(c, c->all_cnt, sizeof(int32_t) * (size_t)npairs));
-  r->rec = c->all_rec.p;
-  r->counts = (int32_t*)c->all_cnt.p;
-  if (!d_b) return gpc_hip_match_sequence_device(c, d_a, W, H, npairs + 1, s, (gpc_correspondence*)r->rec, r->cap, r->counts, d_ncand);
-  StrictScope strict(c);
-  return gpc_hip_match_batch_device(c, d_a, d_b, W, H, npairs, s, (gpc_support*)r->rec, r->cap, r->counts, d_ncand);
-}
-
 // match and score, images as all_records takes them: disparities of pairs, flow of frames
 static int score_match(gpc_hip_ctx* c, const uint8_t* d_a, const uint8_t* d_b, int W, int H, int npairs, const gpc_settings* s,
                        const gpc_truth* truth, const float* thr, int n_thr, gpc_score* d_scores) {
@@ -3555,99 +3530,6 @@ int gpc_hip_score_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W
   if (!c || !d_frames || !d_scores || nframes < 2) return GPC_E_INVALID;
   return score_match(c, d_frames, nullptr, W, H, nframes - 1, s, truth, thr, n_thr, d_scores);
 }
-
-// Host forms of scoring, tracks and filtering: lay out -> upload -> device form -> download, over ONE device block
-// (c->stage) that a call lays out anew: every host form waits for its stream before it returns, so no two are live together.
-//   layout:   in() and out() name the regions in order, each on a 16-byte boundary; alloc() then grows the block once.
-//   upload:   page-locked arrays (gpc_hip_host_alloc) are read where they lie.  Pageable ones pass through the page-locked
-//             arena (host_copy) in pieces of at most 32 MiB, two of them where one does not hold the regions a call (a
-//             chunk) uploads: a piece is written again only when the copies that read it are done (its event, or
-//             wait()).  Two, so that a scoring chunk above 32 MiB (16 pairs of 1024x436 with flow truth: 65 MB) still
-//             goes up without the host waiting for the device, as it did when scoring reserved a chunk's whole size;
-//             tracks and filtering, which had one piece and a wait behind every copy, now hold up to 64 MiB page-locked.
-//             in_bytes counts a records region in full, so two pieces may be reserved where the valid records fit one.
-//             Tracks and filtering send only the valid records of a pair (up_records).
-//   download: small per-pair words land in the page-locked h_cnt and are copied out after the wait; per-pair arrays go to
-//             the caller's arrays as they are, clipped to what the device form wrote, so every other byte there stays.
-// Scoring goes in chunks of at most 16 pairs (frames: GPC_HIP_SEQ_FRAMES, consecutive chunks share one), one wait per chunk;
-// tracks stage the whole call, since links cross pairs; filtering goes in chunks of at most 16 pairs.
-namespace {
-struct Stage {
-  gpc_hip_ctx* c;
-  size_t bytes = 0, in_bytes = 0;  // the block; its regions that are uploaded
-  size_t piece = 0, at = 0;        // the arena of this call's pageable uploads: one or two pieces; the fill of the current one
-  int pieces = 0, cur = 0;
-  bool busy[2] = {false, false};   // copies queued since the last wait() may still read the piece: e_stage[k] says when they are done
-  explicit Stage(gpc_hip_ctx* ctx) : c(ctx) {}
-  size_t out(size_t n) {
-    const size_t region = bytes;
-    bytes += pad16(n);
-    return region;
-  }
-  size_t in(size_t n) {
-    in_bytes += pad16(n);
-    return out(n);
-  }
-  int alloc(size_t word_bytes) {  // word_bytes: what the call lands in h_cnt at a time
-    CHK(ensure(c, c->stage, bytes));
-    return pinned_area(c, word_bytes);
-  }
-  uint8_t* p(size_t region) const { return (uint8_t*)c->stage.p + region; }
-  int wait() {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    at = 0;
-    busy[0] = busy[1] = false;
-    return GPC_OK;
-  }
-  int next_piece() {  // the other piece (where there is one) is filled while the copies out of this one run
-    HIPCHK(c, hipEventRecord(c->e_stage[cur], c->stream));
-    busy[cur] = true;
-    cur = (cur + 1) % pieces;
-    at = 0;
-    if (busy[cur]) HIPCHK(c, hipEventSynchronize(c->e_stage[cur]));
-    busy[cur] = false;
-    return GPC_OK;
-  }
-  int copy_up(size_t region, const uint8_t* src, size_t n, bool pinned) {
-    if (pinned && n) HIPCHK(c, hipMemcpyAsync(p(region), src, n, hipMemcpyHostToDevice, c->stream));
-    if (pinned || !n) return GPC_OK;
-    if (!piece) {  // (once per call)
-      piece = std::min(std::max(in_bytes, pad16(n)), (size_t)32 << 20);
-      pieces = in_bytes > piece ? 2 : 1;
-      uint8_t* d_arena = nullptr;
-      CHK(xfer_reserve(c, pieces * piece, &d_arena));
-      CHK(ensure_pool(c));
-      for (int k = 0; k < pieces; ++k)
-        if (!c->e_stage[k]) HIPCHK(c, c->e_stage[k].create(hipEventDisableTiming));
-    }
-    for (size_t done = 0; done < n;) {
-      if (at == piece) CHK(next_piece());
-      const size_t nb = std::min(n - done, piece - at);
-      uint8_t* h = c->h_xfer.p + cur * piece + at;
-      host_copy(c, h, src + done, nb, true);
-      host_copy_wait(c);
-      HIPCHK(c, hipMemcpyAsync(p(region) + done, h, nb, hipMemcpyHostToDevice, c->stream));
-      at += pad16(nb);
-      done += nb;
-    }
-    return GPC_OK;
-  }
-  int up(size_t region, const void* src, size_t n) { return copy_up(region, (const uint8_t*)src, n, device_view_of_host(src) != nullptr); }
-  // pairs [p0, p0 + pc) of src [..][cap] records of esz bytes -> region [pc][cap]: what lies beyond a pair's count is never read
-  int up_records(size_t region, const void* src, size_t esz, int cap, const int32_t* counts, int p0, int pc) {
-    const bool pinned = device_view_of_host(src) != nullptr;
-    for (int t = 0; t < pc; ++t)
-      CHK(copy_up(region + esz * (size_t)t * cap, (const uint8_t*)src + esz * (size_t)(p0 + t) * cap,
-                  esz * (size_t)valid_records(counts[p0 + t], cap), pinned));
-    return GPC_OK;
-  }
-  // (a pageable dst is written as it is, not through the arena as the note at h_xfer has it: that would be decided here)
-  int down(void* dst, size_t region, size_t n) {
-    HIPCHK(c, hipMemcpyAsync(dst, p(region), n, hipMemcpyDeviceToHost, c->stream));
-    return GPC_OK;
-  }
-};
-}  // namespace
 
 // a chunk's scores -> the caller's array (120 bytes per pair: through h_cnt), then the chunk is done
 static int score_down(Stage& st, size_t region, gpc_score* scores, int n) {
@@ -4215,778 +4097,15 @@ int gpc_hip_track_stream_read_tracks(gpc_hip_ctx* c, gpc_hip_track_stream* s, in
   return GPC_OK;
 }
 
-// ------------------------------------------------------------------ match filtering: grid motion consensus
+}  // extern "C"
 
-static_assert(sizeof(gpc_support) == sizeof(gpc::ConsRec<false>) && sizeof(gpc_correspondence) == sizeof(gpc::ConsRec<true>),
-              "the records and the kernels' view of them");
+// (parts of this translation unit: see the note below the includes at the top)
+#include "host_consensus.h"
+#include "host_refine.h"
+#include "host_pyramid.h"
+#include "host_dense.h"
 
-static int cons_params(const gpc_consensus* p) {
-  if (!p) return GPC_E_INVALID;
-  if (p->cell < 4 || p->cell > 256 || (p->cell & 1) || (p->shifts != 1 && p->shifts != 4)) return GPC_E_INVALID;
-  if (p->alpha_num < 0 || p->alpha_num > 1024 || p->alpha_den < 1 || p->alpha_den > 64) return GPC_E_INVALID;
-  return GPC_OK;
-}
-
-// S and T stay below 2^24 (the products of the test are exact, the kernels multiply 24-bit values), a cell index and a
-// class below 2^26, a record's number in the whole call below 2^31, and a launch has one grid row per pair
-static int cons_limits(long cap, int W, int H, int npairs, int cell) {
-  const long cw = ((long)W + cell - 1) / cell, ch = ((long)H + cell - 1) / cell;
-  if (cap > (1l << 23) || cw * ch > (1l << 22) || npairs > 65535 || (long)npairs * cap > 0x7FFFFFFFl) return GPC_E_UNSUPPORTED;
-  return GPC_OK;
-}
-
-static int cons_args(const gpc_hip_ctx* c, const void* rec, size_t esz, int cap, const void* counts, int W, int H, int npairs,
-                     const gpc_consensus* prm, const void* out, int cap_out, const void* out_counts) {
-  if (!c || !rec || !counts || !out || !out_counts || npairs < 1 || cap <= 0 || cap_out <= 0 || W <= 0 || H <= 0) return GPC_E_INVALID;
-  CHK(cons_params(prm));
-  CHK(cons_limits(cap, W, H, npairs, prm->cell));
-  const uintptr_t r0 = (uintptr_t)rec, r1 = r0 + esz * (size_t)npairs * (size_t)cap;
-  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + esz * (size_t)npairs * (size_t)cap_out;
-  if (r0 < o1 && o0 < r1) return GPC_E_INVALID;  // (kept records are written while later ones are still read)
-  return GPC_OK;
-}
-
-static gpc::ConsGrid cons_grid(int W, int H, const gpc_consensus* prm, int s) {
-  gpc::ConsGrid g;
-  const int cl = prm->cell;
-  g.W = W, g.H = H;
-  g.ox = (s & 1) ? cl / 2 : 0;
-  g.oy = (s & 2) ? cl / 2 : 0;
-  g.gx = (W - 1 + g.ox) / cl + 1;
-  g.gy = (H - 1 + g.oy) / cl + 1;
-  g.ncell = g.gx * g.gy;
-  g.kw = 2u * (uint32_t)g.gx - 1u;
-  g.dc = make_divw(cl);
-  g.dgx = make_divw(g.gx > 1 ? g.gx : 2);
-  g.bit = 1u << s;
-  g.kq = (uint32_t)(prm->alpha_den * prm->alpha_den);
-  g.an2 = (uint32_t)(prm->alpha_num * prm->alpha_num);
-  return g;
-}
-
-// The launches over records already on the device: four per grid, then three that compact.
-extern "C++" {
-template <bool CORR>
-static int cons_filter(gpc_hip_ctx* c, const void* d_rec, int cap, const int32_t* d_counts, int W, int H, int P,
-                       const gpc_consensus* prm, uint8_t* d_keep, void* d_out, int cap_out, int32_t* d_index,
-                       int32_t* d_out_counts) {
-  typedef gpc::ConsRec<CORR> Rec;
-  size_t maxcell = 0;
-  for (int s = 0; s < prm->shifts; ++s) maxcell = std::max(maxcell, (size_t)cons_grid(W, H, prm, s).ncell);
-  const long nchunk = ((long)cap + CS_CHUNK - 1) / CS_CHUNK;
-  CHK(ensure(c, c->cs_key, sizeof(uint32_t) * (size_t)cap * P));
-  CHK(ensure(c, c->cs_idx, sizeof(int32_t) * (size_t)cap * P));
-  CHK(ensure(c, c->cs_cur, sizeof(int32_t) * maxcell * P));
-  CHK(ensure(c, c->cs_start, sizeof(int32_t) * (maxcell + 1) * P));
-  CHK(ensure(c, c->cs_blk, sizeof(int32_t) * (size_t)nchunk * P));
-  if (!d_keep) {
-    CHK(ensure(c, c->cs_keep, (size_t)cap * P));
-    d_keep = (uint8_t*)c->cs_keep.p;
-  }
-  const Rec* rec = (const Rec*)d_rec;
-  uint32_t* skey = (uint32_t*)c->cs_key.p;
-  int32_t* sidx = (int32_t*)c->cs_idx.p;
-  int32_t* cur = (int32_t*)c->cs_cur.p;
-  int32_t* start = (int32_t*)c->cs_start.p;
-  int32_t* blk = (int32_t*)c->cs_blk.p;
-  const long nb = ((long)cap + CS_THREADS - 1) / CS_THREADS;
-  const dim3 sgrid((unsigned)(nb < 1024 ? nb : 1024), P), cgrid((unsigned)nchunk, P);
-  for (int s = 0; s < prm->shifts; ++s) {
-    const gpc::ConsGrid g = cons_grid(W, H, prm, s);
-    HIPCHK(c, hipMemsetAsync(cur, 0, sizeof(int32_t) * (size_t)g.ncell * P, c->stream));
-    {
-      Timed t(c, KID_CONS_CELLS);
-      hipLaunchKernelGGL((gpc::k_cons_cells<CORR>), sgrid, dim3(CS_THREADS), 0, c->stream, rec, cap, d_counts, g, cur, d_keep);
-    }
-    {
-      Timed t(c, KID_CONS_SCAN);
-      hipLaunchKernelGGL((gpc::k_cons_scan<true, true>), dim3(P), dim3(1024), 0, c->stream, cur, (long)g.ncell, g.ncell, start,
-                         (long)g.ncell + 1, (int32_t*)nullptr);
-    }
-    {
-      Timed t(c, KID_CONS_SCATTER);
-      hipLaunchKernelGGL((gpc::k_cons_scatter<CORR>), sgrid, dim3(CS_THREADS), 0, c->stream, rec, cap, d_counts, g, cur, skey, sidx);
-    }
-    {
-      Timed t(c, KID_CONS_COUNT);
-      hipLaunchKernelGGL(gpc::k_cons_count, dim3((unsigned)g.ncell, P), dim3(CS_THREADS), 0, c->stream, cap, g,
-                         (const int32_t*)start, (const uint32_t*)skey, (const int32_t*)sidx, d_keep);
-    }
-  }
-  {
-    Timed t(c, KID_CONS_BLOCKS);
-    hipLaunchKernelGGL(gpc::k_cons_blocks, cgrid, dim3(CS_THREADS), 0, c->stream, cap, d_counts, (const uint8_t*)d_keep, blk, (int)nchunk);
-  }
-  {
-    Timed t(c, KID_CONS_SCAN);
-    hipLaunchKernelGGL((gpc::k_cons_scan<false, false>), dim3(P), dim3(1024), 0, c->stream, blk, nchunk, (int)nchunk, blk, nchunk,
-                       d_out_counts);
-  }
-  {
-    Timed t(c, KID_CONS_WRITE);
-    hipLaunchKernelGGL((gpc::k_cons_write<CORR>), cgrid, dim3(CS_THREADS), 0, c->stream, rec, cap, d_counts, (const uint8_t*)d_keep,
-                       (const int32_t*)blk, (int)nchunk, (Rec*)d_out, cap_out, d_index);
-  }
-  for (int k = KID_CONS_CELLS; k <= KID_CONS_WRITE; ++k) {
-    const bool typed = k == KID_CONS_CELLS || k == KID_CONS_SCATTER || k == KID_CONS_WRITE;
-    // (the scan's slot times both of its instantiations: <true, true> once per grid, <false, false> once for the compaction)
-    snprintf(c->launch_name[k], sizeof c->launch_name[0], k == KID_CONS_SCAN ? "gpc::%s<true, true> + <false, false>" : (typed ? "gpc::%s<%s>" : "gpc::%s"),
-             kKernelNames[k], CORR ? "true" : "false");
-  }
-  HIPCHK(c, hipGetLastError());
-  return GPC_OK;
-}
-}  // extern "C++"
-
-int gpc_hip_consensus_supports_device(gpc_hip_ctx* c, const gpc_support* d_rec, int cap_per_pair, const int32_t* d_counts, int W,
-                                      int H, int npairs, const gpc_consensus* prm, uint8_t* d_keep, gpc_support* d_out, int cap_out,
-                                      int32_t* d_index, int32_t* d_out_counts) {
-  CHK(cons_args(c, d_rec, sizeof(gpc_support), cap_per_pair, d_counts, W, H, npairs, prm, d_out, cap_out, d_out_counts));
-  HIPCHK(c, hipSetDevice(c->device));
-  return cons_filter<false>(c, d_rec, cap_per_pair, d_counts, W, H, npairs, prm, d_keep, d_out, cap_out, d_index, d_out_counts);
-}
-
-int gpc_hip_consensus_correspondences_device(gpc_hip_ctx* c, const gpc_correspondence* d_rec, int cap_per_pair,
-                                             const int32_t* d_counts, int W, int H, int npairs, const gpc_consensus* prm,
-                                             uint8_t* d_keep, gpc_correspondence* d_out, int cap_out, int32_t* d_index,
-                                             int32_t* d_out_counts) {
-  CHK(cons_args(c, d_rec, sizeof(gpc_correspondence), cap_per_pair, d_counts, W, H, npairs, prm, d_out, cap_out, d_out_counts));
-  HIPCHK(c, hipSetDevice(c->device));
-  return cons_filter<true>(c, d_rec, cap_per_pair, d_counts, W, H, npairs, prm, d_keep, d_out, cap_out, d_index, d_out_counts);
-}
-
-// match and filter, images as all_records takes them
-static int cons_match(gpc_hip_ctx* c, const uint8_t* d_a, const uint8_t* d_b, int W, int H, int npairs, const gpc_settings* s,
-                      const gpc_consensus* prm, void* d_out, int cap_out, int32_t* d_out_counts, int32_t* d_raw_counts,
-                      int32_t* d_ncand) {
-  CHK(cons_params(prm));
-  AllRecords r;
-  CHK(all_records_cap(c, s, W, H, !d_b, &r.cap));
-  CHK(cons_limits(r.cap, W, H, npairs, prm->cell));  // (before any workspace is made, too)
-  CHK(all_records(c, d_a, d_b, W, H, npairs, s, d_ncand, &r));
-  if (d_raw_counts)
-    HIPCHK(c, hipMemcpyAsync(d_raw_counts, r.counts, sizeof(int32_t) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
-  return d_b ? cons_filter<false>(c, r.rec, r.cap, r.counts, W, H, npairs, prm, nullptr, d_out, cap_out, nullptr, d_out_counts)
-             : cons_filter<true>(c, r.rec, r.cap, r.counts, W, H, npairs, prm, nullptr, d_out, cap_out, nullptr, d_out_counts);
-}
-
-int gpc_hip_consensus_batch_device(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H, int npairs,
-                                   const gpc_settings* s, const gpc_consensus* prm, gpc_support* d_out, int cap_out,
-                                   int32_t* d_out_counts, int32_t* d_raw_counts, int32_t* d_ncand) {
-  if (!c || !d_rawL || !d_rawR || !d_out || !d_out_counts || npairs <= 0 || cap_out <= 0) return GPC_E_INVALID;
-  return cons_match(c, d_rawL, d_rawR, W, H, npairs, s, prm, d_out, cap_out, d_out_counts, d_raw_counts, d_ncand);
-}
-
-int gpc_hip_consensus_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W, int H, int nframes, const gpc_settings* s,
-                                      const gpc_consensus* prm, gpc_correspondence* d_out, int cap_out, int32_t* d_out_counts,
-                                      int32_t* d_raw_counts, int32_t* d_ncand) {
-  if (!c || !d_frames || !d_out || !d_out_counts || nframes < 2 || cap_out <= 0) return GPC_E_INVALID;
-  return cons_match(c, d_frames, nullptr, W, H, nframes - 1, s, prm, d_out, cap_out, d_out_counts, d_raw_counts, d_ncand);
-}
-
-// Host forms (Stage): chunks of at most 16 pairs.
-extern "C++" {
-template <bool CORR>
-static int cons_host(gpc_hip_ctx* c, const void* rec, int cap, const int32_t* counts, int W, int H, int npairs,
-                     const gpc_consensus* prm, uint8_t* keep, void* out, int cap_out, int32_t* index, int32_t* out_counts) {
-  const size_t esz = sizeof(gpc::ConsRec<CORR>);
-  CHK(cons_args(c, rec, esz, cap, counts, W, H, npairs, prm, out, cap_out, out_counts));
-  CHK(host_call_begin(c));
-  const int K = npairs < 16 ? npairs : 16;
-  Stage st(c);
-  const size_t r_rec = st.in(esz * (size_t)cap * K), r_cnt = st.in(sizeof(int32_t) * (size_t)K), r_keep = st.out((size_t)cap * K);
-  const size_t r_out = st.out(esz * (size_t)cap_out * K), r_idx = st.out(sizeof(int32_t) * (size_t)cap_out * K);
-  const size_t r_n = st.out(sizeof(int32_t) * (size_t)K);
-  CHK(st.alloc(sizeof(int32_t) * (size_t)K));
-  int status = GPC_OK;
-  for (int p0 = 0; p0 < npairs; p0 += K) {
-    const int pc = npairs - p0 < K ? npairs - p0 : K;
-    CHK(st.up(r_cnt, counts + p0, sizeof(int32_t) * (size_t)pc));
-    CHK(st.up_records(r_rec, rec, esz, cap, counts, p0, pc));
-    CHK(cons_filter<CORR>(c, st.p(r_rec), cap, (const int32_t*)st.p(r_cnt), W, H, pc, prm, keep ? st.p(r_keep) : nullptr, st.p(r_out),
-                          cap_out, index ? (int32_t*)st.p(r_idx) : nullptr, (int32_t*)st.p(r_n)));
-    CHK(st.down(c->h_cnt.p, r_n, sizeof(int32_t) * (size_t)pc));
-    CHK(st.wait());
-    for (int t = 0; t < pc; ++t) {  // a pair's keep bytes as far as its records go, its kept records and their indices as far as cap_out
-      const size_t m = (size_t)valid_records(counts[p0 + t], cap), w = (size_t)valid_records(c->h_cnt.p[t], cap_out), q = (size_t)(p0 + t);
-      if (c->h_cnt.p[t] > cap_out) status = GPC_E_CAPACITY;
-      if (keep && m) CHK(st.down(keep + q * cap, r_keep + (size_t)t * cap, m));
-      if (w) CHK(st.down((uint8_t*)out + esz * q * cap_out, r_out + esz * (size_t)t * cap_out, esz * w));
-      if (w && index) CHK(st.down(index + q * cap_out, r_idx + sizeof(int32_t) * (size_t)t * cap_out, sizeof(int32_t) * w));
-    }
-    CHK(st.wait());
-    memcpy(out_counts + p0, c->h_cnt.p, sizeof(int32_t) * (size_t)pc);
-  }
-  CHK(check_join_err(c));
-  return status;
-}
-}  // extern "C++"
-
-int gpc_hip_consensus_supports(gpc_hip_ctx* c, const gpc_support* rec, int cap_per_pair, const int32_t* counts, int W, int H,
-                               int npairs, const gpc_consensus* prm, uint8_t* keep, gpc_support* out, int cap_out, int32_t* index,
-                               int32_t* out_counts) {
-  return cons_host<false>(c, rec, cap_per_pair, counts, W, H, npairs, prm, keep, out, cap_out, index, out_counts);
-}
-
-int gpc_hip_consensus_correspondences(gpc_hip_ctx* c, const gpc_correspondence* rec, int cap_per_pair, const int32_t* counts, int W,
-                                      int H, int npairs, const gpc_consensus* prm, uint8_t* keep, gpc_correspondence* out,
-                                      int cap_out, int32_t* index, int32_t* out_counts) {
-  return cons_host<true>(c, rec, cap_per_pair, counts, W, H, npairs, prm, keep, out, cap_out, index, out_counts);
-}
-
-// ------------------------------------------------------------------ match refinement: sub-pixel position and photometric cost
-
-static_assert(sizeof(gpc_refinement) == sizeof(uint2), "the results and the kernel's view of them");
-
-// rec / out: [npairs][cap] records of esz bytes
-static int refine_args(const gpc_hip_ctx* c, const void* rec, size_t esz, int cap, const void* counts, const void* imgL,
-                       const void* imgR, int W, int H, int npairs, int radius, const void* ref, const void* out) {
-  if (!c || !rec || !counts || !imgL || !imgR || !ref || npairs < 1 || cap < 1 || W < 1 || H < 1) return GPC_E_INVALID;
-  if (radius < 1 || radius > RF_MAX_RADIUS) return GPC_E_INVALID;
-  // a launch has one grid row per pair, a record's number in the whole call and a pixel's in an image fit an int
-  if (npairs > 65535 || (long)npairs * cap > 0x7FFFFFFFl || (long)W * H > (1l << 30)) return GPC_E_UNSUPPORTED;
-  if (out) {
-    const uintptr_t r0 = (uintptr_t)rec, r1 = r0 + esz * (size_t)npairs * (size_t)cap, o0 = (uintptr_t)out;
-    if (r0 < o0 + esz * (size_t)npairs * (size_t)cap && o0 < r1) return GPC_E_INVALID;  // (the kernel reads and writes without order)
-  }
-  return GPC_OK;
-}
-
-// The launch over records and images already on the device.
-extern "C++" {
-template <bool CORR, int R>
-static void refine_launch(gpc_hip_ctx* c, dim3 grid, const void* d_rec, int cap, const int32_t* d_counts, const uint8_t* d_L,
-                          const uint8_t* d_R, int W, int H, gpc_refinement* d_ref, gpc_support* d_out) {
-  hipLaunchKernelGGL((gpc::k_refine<CORR, R>), grid, dim3(RF_THREADS), 0, c->stream, (const gpc::ConsRec<CORR>*)d_rec, cap, d_counts,
-                     d_L, d_R, W, H, (uint2*)d_ref, (gpc::ConsRec<false>*)d_out);
-}
-
-template <bool CORR>
-static int refine_records(gpc_hip_ctx* c, const void* d_rec, int cap, const int32_t* d_counts, const uint8_t* d_L, const uint8_t* d_R,
-                          int W, int H, int P, int radius, gpc_refinement* d_ref, gpc_support* d_out) {
-  const long nb = ((long)cap + RF_THREADS - 1) / RF_THREADS;
-  const dim3 grid((unsigned)(nb < 4096 ? nb : 4096), P);
-  {
-    Timed t(c, KID_REFINE);
-    switch (radius) {
-      case 1: refine_launch<CORR, 1>(c, grid, d_rec, cap, d_counts, d_L, d_R, W, H, d_ref, d_out); break;
-      case 2: refine_launch<CORR, 2>(c, grid, d_rec, cap, d_counts, d_L, d_R, W, H, d_ref, d_out); break;
-      case 3: refine_launch<CORR, 3>(c, grid, d_rec, cap, d_counts, d_L, d_R, W, H, d_ref, d_out); break;
-      case 4: refine_launch<CORR, 4>(c, grid, d_rec, cap, d_counts, d_L, d_R, W, H, d_ref, d_out); break;
-      case 5: refine_launch<CORR, 5>(c, grid, d_rec, cap, d_counts, d_L, d_R, W, H, d_ref, d_out); break;
-      default: refine_launch<CORR, 6>(c, grid, d_rec, cap, d_counts, d_L, d_R, W, H, d_ref, d_out); break;
-    }
-  }
-  snprintf(c->launch_name[KID_REFINE], sizeof c->launch_name[0], "gpc::k_refine<%s, %d>", CORR ? "true" : "false", radius);
-  HIPCHK(c, hipGetLastError());
-  return GPC_OK;
-}
-}  // extern "C++"
-
-int gpc_hip_refine_supports_device(gpc_hip_ctx* c, const gpc_support* d_rec, int cap_per_pair, const int32_t* d_counts,
-                                   const uint8_t* d_imgL, const uint8_t* d_imgR, int W, int H, int npairs, int radius,
-                                   gpc_refinement* d_ref, gpc_support* d_out) {
-  CHK(refine_args(c, d_rec, sizeof(gpc_support), cap_per_pair, d_counts, d_imgL, d_imgR, W, H, npairs, radius, d_ref, d_out));
-  HIPCHK(c, hipSetDevice(c->device));
-  return refine_records<false>(c, d_rec, cap_per_pair, d_counts, d_imgL, d_imgR, W, H, npairs, radius, d_ref, d_out);
-}
-
-int gpc_hip_refine_correspondences_device(gpc_hip_ctx* c, const gpc_correspondence* d_rec, int cap_per_pair, const int32_t* d_counts,
-                                          const uint8_t* d_imgL, const uint8_t* d_imgR, int W, int H, int npairs, int radius,
-                                          gpc_refinement* d_ref) {
-  CHK(refine_args(c, d_rec, sizeof(gpc_correspondence), cap_per_pair, d_counts, d_imgL, d_imgR, W, H, npairs, radius, d_ref, nullptr));
-  HIPCHK(c, hipSetDevice(c->device));
-  return refine_records<true>(c, d_rec, cap_per_pair, d_counts, d_imgL, d_imgR, W, H, npairs, radius, d_ref, nullptr);
-}
-
-// Match, then refine over the raw images.  The match is the plain call on the context itself (lanes drained, as
-// all_records has it): what it refuses is refused, its status is the call's.
-int gpc_hip_refine_batch_device(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H, int npairs,
-                                const gpc_settings* s, int radius, gpc_support* d_supports, int cap_per_pair, int32_t* d_counts,
-                                int32_t* d_ncand, gpc_refinement* d_ref, gpc_support* d_out) {
-  if (!c || !d_rawL || !d_rawR || !d_supports || !d_counts || npairs <= 0 || cap_per_pair <= 0) return GPC_E_INVALID;
-  CHK(check_settings(s));
-  CHK(check_dims(W, H));
-  CHK(refine_args(c, d_supports, sizeof(gpc_support), cap_per_pair, d_counts, d_rawL, d_rawR, W, H, npairs, radius, d_ref, d_out));
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->pipeline > 1) CHK(drain_lanes(c));
-  {
-    StrictScope strict(c);
-    CHK(gpc_hip_match_batch_device(c, d_rawL, d_rawR, W, H, npairs, s, d_supports, cap_per_pair, d_counts, d_ncand));
-  }
-  return refine_records<false>(c, d_supports, cap_per_pair, d_counts, d_rawL, d_rawR, W, H, npairs, radius, d_ref, d_out);
-}
-
-int gpc_hip_refine_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W, int H, int nframes, const gpc_settings* s,
-                                   int radius, gpc_correspondence* d_corr, int cap_per_pair, int32_t* d_counts, int32_t* d_ncand,
-                                   gpc_refinement* d_ref) {
-  if (!c || !d_frames || !d_corr || !d_counts || nframes < 2 || cap_per_pair <= 0) return GPC_E_INVALID;
-  CHK(match_usable(c, s, W, H, true));
-  const uint8_t* d_next = d_frames + (size_t)W * H;
-  CHK(refine_args(c, d_corr, sizeof(gpc_correspondence), cap_per_pair, d_counts, d_frames, d_next, W, H, nframes - 1, radius, d_ref, nullptr));
-  CHK(gpc_hip_match_sequence_device(c, d_frames, W, H, nframes, s, d_corr, cap_per_pair, d_counts, d_ncand));
-  return refine_records<true>(c, d_corr, cap_per_pair, d_counts, d_frames, d_next, W, H, nframes - 1, radius, d_ref, nullptr);
-}
-
-// Host forms (Stage): chunks of at most 16 pairs -- their records as far as their counts go, their counts, both images.
-extern "C++" {
-template <bool CORR>
-static int refine_host(gpc_hip_ctx* c, const void* rec, int cap, const int32_t* counts, const uint8_t* imgL, const uint8_t* imgR, int W,
-                       int H, int npairs, int radius, gpc_refinement* ref, gpc_support* out) {
-  const size_t esz = sizeof(gpc::ConsRec<CORR>);
-  CHK(refine_args(c, rec, esz, cap, counts, imgL, imgR, W, H, npairs, radius, ref, out));
-  CHK(host_call_begin(c));
-  const int K = npairs < 16 ? npairs : 16;
-  const size_t n = (size_t)W * H;
-  Stage st(c);
-  const size_t r_rec = st.in(esz * (size_t)cap * K), r_cnt = st.in(sizeof(int32_t) * (size_t)K), r_L = st.in(n * K), r_R = st.in(n * K);
-  const size_t r_ref = st.out(sizeof(gpc_refinement) * (size_t)cap * K), r_out = st.out(out ? esz * (size_t)cap * K : 0);
-  CHK(st.alloc(0));
-  for (int p0 = 0; p0 < npairs; p0 += K) {
-    const int pc = npairs - p0 < K ? npairs - p0 : K;
-    CHK(st.up(r_cnt, counts + p0, sizeof(int32_t) * (size_t)pc));
-    CHK(st.up_records(r_rec, rec, esz, cap, counts, p0, pc));
-    CHK(st.up(r_L, imgL + n * p0, n * pc));
-    CHK(st.up(r_R, imgR + n * p0, n * pc));
-    CHK(refine_records<CORR>(c, st.p(r_rec), cap, (const int32_t*)st.p(r_cnt), st.p(r_L), st.p(r_R), W, H, pc, radius,
-                             (gpc_refinement*)st.p(r_ref), out ? (gpc_support*)st.p(r_out) : nullptr));
-    for (int t = 0; t < pc; ++t) {  // a pair's results as far as its records go
-      const size_t m = (size_t)valid_records(counts[p0 + t], cap), q = (size_t)(p0 + t);
-      if (!m) continue;
-      CHK(st.down(ref + q * cap, r_ref + sizeof(gpc_refinement) * (size_t)t * cap, sizeof(gpc_refinement) * m));
-      if (out) CHK(st.down(out + q * cap, r_out + esz * (size_t)t * cap, esz * m));
-    }
-    CHK(st.wait());
-  }
-  return check_join_err(c);
-}
-}  // extern "C++"
-
-int gpc_hip_refine_supports(gpc_hip_ctx* c, const gpc_support* rec, int cap_per_pair, const int32_t* counts, const uint8_t* imgL,
-                            const uint8_t* imgR, int W, int H, int npairs, int radius, gpc_refinement* ref, gpc_support* out) {
-  return refine_host<false>(c, rec, cap_per_pair, counts, imgL, imgR, W, H, npairs, radius, ref, out);
-}
-
-int gpc_hip_refine_correspondences(gpc_hip_ctx* c, const gpc_correspondence* rec, int cap_per_pair, const int32_t* counts,
-                                   const uint8_t* imgL, const uint8_t* imgR, int W, int H, int npairs, int radius,
-                                   gpc_refinement* ref) {
-  return refine_host<true>(c, rec, cap_per_pair, counts, imgL, imgR, W, H, npairs, radius, ref, nullptr);
-}
-
-// ------------------------------------------------------------------ matching over an image pyramid
-
-static_assert(GPC_MAX_PYRAMID_LEVELS == 4, "a block is at most 8 bits of one plane word (k_pyramid.h)");
-
-// one downsampling step over nimages images already on the device
-static int pyr_down(gpc_hip_ctx* c, const uint8_t* d_src, int W, int H, int nimages, uint8_t* d_dst) {
-  const dim3 grid((W / 8 + PY_DOWN_COLS - 1) / PY_DOWN_COLS, (H / 2 + PY_DOWN_ROWS - 1) / PY_DOWN_ROWS, nimages);
-  {
-    Timed t(c, KID_PYR_DOWN);
-    hipLaunchKernelGGL(gpc::k_pyr_down, grid, dim3(PY_DOWN_COLS * PY_DOWN_ROWS), 0, c->stream, d_src, W, H, d_dst);
-  }
-  snprintf(c->launch_name[KID_PYR_DOWN], sizeof c->launch_name[0], "gpc::k_pyr_down");
-  HIPCHK(c, hipGetLastError());
-  return GPC_OK;
-}
-
-int gpc_hip_pyramid_levels(int W, int H, int levels, int32_t* widths, int32_t* heights) {
-  return gpc::pyr_levels(W, H, levels, widths, heights);
-}
-
-int gpc_hip_pyramid_down_device(gpc_hip_ctx* c, const uint8_t* d_src, int W, int H, int nimages, uint8_t* d_dst) {
-  if (!c) return GPC_E_INVALID;
-  CHK(gpc::pyr_down_check(d_src, d_dst, W, H, nimages));
-  HIPCHK(c, hipSetDevice(c->device));
-  return pyr_down(c, d_src, W, H, nimages, d_dst);
-}
-
-// The merge over records on the device: d_rec[l] = [npairs][caps[l]] unmapped level-l records, d_cnt[l] their counts.
-extern "C++" {
-template <bool CORR>
-static int pyr_merge(gpc_hip_ctx* c, const void* const* d_rec, const int32_t* caps, const int32_t* const* d_cnt, int W, int H,
-                     int npairs, int levels, void* d_out, int cap, int32_t* d_counts, int32_t* d_level_counts) {
-  if (!c || !d_rec || !d_cnt || !d_out || !d_counts || !d_level_counts) return GPC_E_INVALID;
-  CHK(gpc::pyr_merge_check(W, H, npairs, levels, caps, cap));
-  for (int l = 0; l < levels; ++l)
-    if (!d_rec[l] || !d_cnt[l]) return GPC_E_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  const int wpr = (W + 31) / 32;
-  int most = 0;
-  for (int l = 0; l < levels; ++l) most = std::max(most, (caps[l] + PY_CHUNK - 1) / PY_CHUNK);
-  CHK(ensure(c, c->py_plane, sizeof(uint32_t) * (size_t)wpr * H * npairs));
-  CHK(ensure(c, c->py_flags, sizeof(uint64_t) * (PY_CHUNK / 64) * (size_t)most * npairs));
-  CHK(ensure(c, c->py_blk, sizeof(int32_t) * (size_t)most * npairs));
-  uint32_t* plane = (uint32_t*)c->py_plane.p;
-  unsigned long long* flags = (unsigned long long*)c->py_flags.p;
-  int32_t* blk = (int32_t*)c->py_blk.p;
-  if (levels > 1) HIPCHK(c, hipMemsetAsync(plane, 0, sizeof(uint32_t) * (size_t)wpr * H * npairs, c->stream));
-  const int stride = (int)(sizeof(gpc::PyRec<CORR>) / sizeof(int32_t));
-  for (int l = 0; l < levels; ++l) {
-    const int nchunk = (caps[l] + PY_CHUNK - 1) / PY_CHUNK;
-    const dim3 grid(nchunk, npairs);
-    {
-      Timed t(c, KID_PYR_KEEP);
-      hipLaunchKernelGGL(gpc::k_pyr_keep, grid, dim3(PY_THREADS), 0, c->stream, (const int32_t*)d_rec[l], stride, (long)caps[l],
-                         d_cnt[l], l, W >> l, H >> l, (const uint32_t*)plane, wpr, H, flags, blk, nchunk);
-    }
-    {
-      Timed t(c, KID_PYR_SCAN);
-      hipLaunchKernelGGL(gpc::k_pyr_scan, dim3(npairs), dim3(nchunk >= 1024 ? 1024 : 64 * ((nchunk + 63) / 64)), 0, c->stream, blk,
-                         nchunk, l == 0 ? 1 : 0, d_level_counts + (size_t)l * npairs, d_counts);
-    }
-    {
-      Timed t(c, KID_PYR_WRITE);
-      hipLaunchKernelGGL((gpc::k_pyr_write<CORR>), grid, dim3(PY_THREADS), 0, c->stream, (const gpc::PyRec<CORR>*)d_rec[l],
-                         (long)caps[l], l, W >> l, H >> l, (const unsigned long long*)flags, (const int32_t*)blk, nchunk,
-                         (gpc::PyRec<CORR>*)d_out, (long)cap, plane, wpr, H, l + 1 < levels ? 1 : 0);
-    }
-    HIPCHK(c, hipGetLastError());
-  }
-  snprintf(c->launch_name[KID_PYR_KEEP], sizeof c->launch_name[0], "gpc::k_pyr_keep");
-  snprintf(c->launch_name[KID_PYR_SCAN], sizeof c->launch_name[0], "gpc::k_pyr_scan");
-  snprintf(c->launch_name[KID_PYR_WRITE], sizeof c->launch_name[0], "gpc::k_pyr_write<%s>", CORR ? "true" : "false");
-  return GPC_OK;
-}
-}  // extern "C++"
-
-int gpc_hip_pyramid_merge_supports_device(gpc_hip_ctx* c, const gpc_support* const* d_rec, const int32_t* caps,
-                                          const int32_t* const* d_cnt, int W, int H, int npairs, int levels, gpc_support* d_out,
-                                          int cap_per_pair, int32_t* d_counts, int32_t* d_level_counts) {
-  return pyr_merge<false>(c, (const void* const*)d_rec, caps, d_cnt, W, H, npairs, levels, d_out, cap_per_pair, d_counts,
-                          d_level_counts);
-}
-
-int gpc_hip_pyramid_merge_correspondences_device(gpc_hip_ctx* c, const gpc_correspondence* const* d_rec, const int32_t* caps,
-                                                 const int32_t* const* d_cnt, int W, int H, int npairs, int levels,
-                                                 gpc_correspondence* d_out, int cap_per_pair, int32_t* d_counts,
-                                                 int32_t* d_level_counts) {
-  return pyr_merge<true>(c, (const void* const*)d_rec, caps, d_cnt, W, H, npairs, levels, d_out, cap_per_pair, d_counts,
-                         d_level_counts);
-}
-
-namespace {
-// The forest counts as one of a level's size while that level is matched: its tests are offsets within the 27x27 patch
-// (GpcForestDev holds no width), so they apply to an image of any size; what the context remembers of the forest (its
-// size, its source, the generation of the codes) is what it was when the scope ends.
-struct LevelScope {
-  gpc_hip_ctx* c;
-  int w, h;
-  LevelScope(gpc_hip_ctx* ctx, int W, int H) : c(ctx), w(ctx->forest_w), h(ctx->forest_h) {
-    c->forest_w = W;
-    c->forest_h = H;
-  }
-  ~LevelScope() {
-    c->forest_w = w;
-    c->forest_h = h;
-  }
-};
-}  // namespace
-
-// what a pyramid call refuses, before any workspace is made; ws / hs: the levels' sizes
-static int pyr_usable(gpc_hip_ctx* c, const gpc_settings* s, int W, int H, int levels, int32_t* ws, int32_t* hs) {
-  CHK(check_settings(s));
-  CHK(gpc::pyr_levels(W, H, levels, ws, hs));
-  CHK(forest_matches(c, W, H));
-  if (c->ngroups > 1) return GPC_E_UNSUPPORTED;
-  if (gpc::pyr_level_cap(W, H) > 0x7FFFFFFFll) return GPC_E_UNSUPPORTED;
-  return GPC_OK;
-}
-
-// d_b null: d_a holds npairs + 1 frames (correspondences); else the left and right images of npairs pairs (supports).
-// Every level is downsampled from the level before, matched by the plain call at its own size with its own settings into a
-// workspace that holds every record, and the levels are merged into the caller's arrays.
-extern "C++" {
-template <bool CORR>
-static int pyr_match(gpc_hip_ctx* c, const uint8_t* d_a, const uint8_t* d_b, int W, int H, int npairs, int levels,
-                     const gpc_settings* s, void* d_out, int cap, int32_t* d_counts, int32_t* d_level_counts, int32_t* d_ncand) {
-  int32_t ws[GPC_MAX_PYRAMID_LEVELS], hs[GPC_MAX_PYRAMID_LEVELS];
-  CHK(pyr_usable(c, s, W, H, levels, ws, hs));
-  if (npairs > 65535) return GPC_E_UNSUPPORTED;
-  if (levels > 1) {  // (the downsampling step reads 8 bytes at a time)
-    CHK(gpc::pyr_down_check(d_a, d_out, W, H, CORR ? npairs + 1 : npairs));
-    if (!CORR) CHK(gpc::pyr_down_check(d_b, d_out, W, H, npairs));
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->pipeline > 1) CHK(drain_lanes(c));
-  StrictScope strict(c);
-  const int nimg = CORR ? npairs + 1 : npairs;          // images per side
-  const size_t ncs = CORR ? (size_t)nimg : 2 * (size_t)npairs;  // candidate counts per level
-  auto match = [&](int l, const uint8_t* a, const uint8_t* b, void* rec, int rcap, int32_t* cnt) -> int {
-    const gpc_settings sl = gpc::pyr_level_settings(*s, l);
-    int32_t* nc = d_ncand ? d_ncand + (size_t)l * ncs : nullptr;
-    LevelScope level(c, ws[l], hs[l]);
-    if (CORR) return gpc_hip_match_sequence_device(c, a, ws[l], hs[l], nimg, &sl, (gpc_correspondence*)rec, rcap, cnt, nc);
-    return gpc_hip_match_batch_device(c, a, b, ws[l], hs[l], npairs, &sl, (gpc_support*)rec, rcap, cnt, nc);
-  };
-  if (levels == 1) {  // the plain call, into the caller's arrays
-    CHK(match(0, d_a, d_b, d_out, cap, d_counts));
-    HIPCHK(c, hipMemcpyAsync(d_level_counts, d_counts, sizeof(int32_t) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
-    return GPC_OK;
-  }
-  const size_t esz = sizeof(gpc::PyRec<CORR>);
-  size_t img_at[GPC_MAX_PYRAMID_LEVELS] = {0}, rec_at[GPC_MAX_PYRAMID_LEVELS] = {0}, img_bytes = 0, rec_bytes = 0;
-  int32_t caps[GPC_MAX_PYRAMID_LEVELS];
-  for (int l = 0; l < levels; ++l) {
-    caps[l] = (int32_t)gpc::pyr_level_cap(ws[l], hs[l]);
-    rec_at[l] = rec_bytes;
-    rec_bytes += pad16(esz * (size_t)caps[l] * npairs);
-    if (!l) continue;
-    img_at[l] = img_bytes;
-    img_bytes += pad16((size_t)ws[l] * hs[l] * nimg) * (CORR ? 1 : 2);
-  }
-  CHK(ensure(c, c->py_img, img_bytes));
-  CHK(ensure(c, c->py_rec, rec_bytes));
-  CHK(ensure(c, c->py_cnt, sizeof(int32_t) * (size_t)levels * npairs));
-  const void* d_rec[GPC_MAX_PYRAMID_LEVELS];
-  const int32_t* d_cnt[GPC_MAX_PYRAMID_LEVELS];
-  const uint8_t *a = d_a, *b = d_b;
-  for (int l = 0; l < levels; ++l) {
-    if (l) {
-      uint8_t* na = (uint8_t*)c->py_img.p + img_at[l];
-      uint8_t* nb = CORR ? nullptr : na + pad16((size_t)ws[l] * hs[l] * nimg);
-      CHK(pyr_down(c, a, ws[l - 1], hs[l - 1], nimg, na));
-      if (!CORR) CHK(pyr_down(c, b, ws[l - 1], hs[l - 1], nimg, nb));
-      a = na;
-      b = nb;
-    }
-    void* rec = (uint8_t*)c->py_rec.p + rec_at[l];
-    int32_t* cnt = (int32_t*)c->py_cnt.p + (size_t)l * npairs;
-    CHK(match(l, a, b, rec, caps[l], cnt));
-    d_rec[l] = rec;
-    d_cnt[l] = cnt;
-  }
-  return pyr_merge<CORR>(c, d_rec, caps, d_cnt, W, H, npairs, levels, d_out, cap, d_counts, d_level_counts);
-}
-}  // extern "C++"
-
-int gpc_hip_pyramid_batch_device(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H, int npairs, int levels,
-                                 const gpc_settings* s, gpc_support* d_out, int cap_per_pair, int32_t* d_counts,
-                                 int32_t* d_level_counts, int32_t* d_ncand) {
-  if (!c || !d_rawL || !d_rawR || !d_out || !d_counts || !d_level_counts || npairs <= 0 || cap_per_pair <= 0) return GPC_E_INVALID;
-  return pyr_match<false>(c, d_rawL, d_rawR, W, H, npairs, levels, s, d_out, cap_per_pair, d_counts, d_level_counts, d_ncand);
-}
-
-int gpc_hip_pyramid_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W, int H, int nframes, int levels,
-                                    const gpc_settings* s, gpc_correspondence* d_out, int cap_per_pair, int32_t* d_counts,
-                                    int32_t* d_level_counts, int32_t* d_ncand) {
-  if (!c || !d_frames || !d_out || !d_counts || !d_level_counts || nframes < 2 || cap_per_pair <= 0) return GPC_E_INVALID;
-  return pyr_match<true>(c, d_frames, nullptr, W, H, nframes - 1, levels, s, d_out, cap_per_pair, d_counts, d_level_counts,
-                         d_ncand);
-}
-
-// Host forms (Stage): chunks of at most 16 pairs, or of the pairs of GPC_HIP_SEQ_FRAMES frames (consecutive chunks share
-// one).  b null: a holds npairs + 1 frames.  A chunk's counts, level counts and candidate counts land in h_cnt; its records
-// go to the caller's array as far as the device form wrote them.
-extern "C++" {
-template <bool CORR>
-static int pyr_host(gpc_hip_ctx* c, const uint8_t* a, const uint8_t* b, int W, int H, int npairs, int levels, const gpc_settings* s,
-                    void* out, int cap, int32_t* counts, int32_t* level_counts, int32_t* ncand) {
-  int32_t ws[GPC_MAX_PYRAMID_LEVELS], hs[GPC_MAX_PYRAMID_LEVELS];
-  CHK(pyr_usable(c, s, W, H, levels, ws, hs));
-  CHK(host_call_begin(c));
-  const size_t n = (size_t)W * H, esz = sizeof(gpc::PyRec<CORR>);
-  const int seq = CORR ? 1 : 0;
-  const int most = CORR ? (c->seq_frames > 1 && c->seq_frames < 16 ? c->seq_frames : 16) - 1 : 16;
-  const int K = npairs < most ? npairs : most;
-  const size_t ncs = CORR ? (size_t)K + 1 : 2 * (size_t)K;  // candidate counts of a full chunk, per level
-  const size_t total_ncs = CORR ? (size_t)npairs + 1 : 2 * (size_t)npairs;
-  Stage st(c);
-  const size_t r_a = st.in(n * (K + seq)), r_b = st.in(CORR ? 0 : n * K), r_out = st.out(esz * (size_t)cap * K);
-  const size_t r_cnt = st.out(sizeof(int32_t) * (size_t)K), r_lc = st.out(sizeof(int32_t) * (size_t)levels * K);
-  const size_t r_nc = st.out(sizeof(int32_t) * levels * ncs);
-  CHK(st.alloc(sizeof(int32_t) * ((size_t)K + (size_t)levels * K + levels * ncs)));
-  int status = GPC_OK;
-  for (int p0 = 0; p0 < npairs; p0 += K) {
-    const int pc = npairs - p0 < K ? npairs - p0 : K;
-    const size_t cs = CORR ? (size_t)pc + 1 : 2 * (size_t)pc;
-    CHK(st.up(r_a, a + n * p0, n * (pc + seq)));
-    if (!CORR) CHK(st.up(r_b, b + n * p0, n * pc));
-    CHK(pyr_match<CORR>(c, st.p(r_a), CORR ? nullptr : st.p(r_b), W, H, pc, levels, s, st.p(r_out), cap, (int32_t*)st.p(r_cnt),
-                        (int32_t*)st.p(r_lc), (int32_t*)st.p(r_nc)));
-    int32_t *h_n = c->h_cnt.p, *h_lc = h_n + K, *h_nc = h_lc + (size_t)levels * K;
-    CHK(st.down(h_n, r_cnt, sizeof(int32_t) * (size_t)pc));
-    CHK(st.down(h_lc, r_lc, sizeof(int32_t) * (size_t)levels * pc));
-    CHK(st.down(h_nc, r_nc, sizeof(int32_t) * levels * cs));
-    CHK(st.wait());
-    for (int t = 0; t < pc; ++t) {
-      const size_t w = (size_t)valid_records(h_n[t], cap), q = (size_t)(p0 + t);
-      if (h_n[t] > cap) status = GPC_E_CAPACITY;
-      if (w) CHK(st.down((uint8_t*)out + esz * q * cap, r_out + esz * (size_t)t * cap, esz * w));
-      counts[q] = h_n[t];
-      for (int l = 0; l < levels; ++l) level_counts[(size_t)l * npairs + q] = h_lc[(size_t)l * pc + t];
-    }
-    if (ncand)
-      for (int l = 0; l < levels; ++l)
-        memcpy(ncand + l * total_ncs + (CORR ? (size_t)p0 : 2 * (size_t)p0), h_nc + l * cs, sizeof(int32_t) * cs);
-    CHK(st.wait());
-  }
-  CHK(check_join_err(c));
-  return status;
-}
-}  // extern "C++"
-
-int gpc_hip_pyramid_batch(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, int W, int H, int npairs, int levels,
-                          const gpc_settings* s, gpc_support* out, int cap_per_pair, int32_t* counts, int32_t* level_counts,
-                          int32_t* ncand) {
-  if (!c || !rawL || !rawR || !out || !counts || !level_counts || npairs <= 0 || cap_per_pair <= 0) return GPC_E_INVALID;
-  return pyr_host<false>(c, rawL, rawR, W, H, npairs, levels, s, out, cap_per_pair, counts, level_counts, ncand);
-}
-
-int gpc_hip_pyramid_sequence(gpc_hip_ctx* c, const uint8_t* frames, int W, int H, int nframes, int levels, const gpc_settings* s,
-                             gpc_correspondence* out, int cap_per_pair, int32_t* counts, int32_t* level_counts, int32_t* ncand) {
-  if (!c || !frames || !out || !counts || !level_counts || nframes < 2 || cap_per_pair <= 0) return GPC_E_INVALID;
-  return pyr_host<true>(c, frames, nullptr, W, H, nframes - 1, levels, s, out, cap_per_pair, counts, level_counts, ncand);
-}
-
-// ------------------------------------------------------------------ dense maps from sparse matches: the hierarchical fill
-
-static_assert(sizeof(gpc_densify) == 16 && GPC_DENSE_NONE == DN_NONE, "the parameters and the kernels' view of none");
-
-static int dense_args(const gpc_hip_ctx* c, const void* rec, int cap, const void* counts, const void* ref, int W, int H, int npairs,
-                      const gpc_densify* prm, const void* value) {
-  if (!c || !rec || !counts || !value) return GPC_E_INVALID;
-  CHK(gpc::dn_params(prm, ref != nullptr));
-  return gpc::dn_limits(W, H, npairs, cap);
-}
-
-// The launches over records already on the device: clear and claim the owner plane, pull, the levels above the tile, push.
-extern "C++" {
-template <bool CORR>
-static int dense_fill(gpc_hip_ctx* c, const void* d_rec, int cap, const int32_t* d_counts, const gpc_refinement* d_ref, int W, int H,
-                      int P, const gpc_densify* prm, int32_t* d_value, uint8_t* d_level) {
-  typedef gpc::ConsRec<CORR> Rec;
-  constexpr int C = CORR ? 2 : 1;
-  const gpc::DnGeom g = gpc::dn_geom(W, H, *prm);
-  const long cells = (long)gpc::dn_cells(g);
-  CHK(ensure(c, c->dn_owner, (size_t)gpc::dn_owner_bytes(W, H, P)));
-  CHK(ensure(c, c->dn_n, (size_t)gpc::dn_count_bytes(g, P)));
-  CHK(ensure(c, c->dn_s, (size_t)gpc::dn_sum_bytes(g, P, C)));
-  uint32_t* owner = (uint32_t*)c->dn_owner.p;
-  int32_t* pn = (int32_t*)c->dn_n.p;
-  int64_t* ps = (int64_t*)c->dn_s.p;
-  const uint2* ref = (const uint2*)d_ref;
-  HIPCHK(c, hipMemsetAsync(owner, 0xFF, (size_t)gpc::dn_owner_bytes(W, H, P), c->stream));
-  const long nb = ((long)cap + DN_THREADS - 1) / DN_THREADS;
-  const dim3 tiles((unsigned)((W + DN_TILE - 1) / DN_TILE), (unsigned)((H + DN_TILE - 1) / DN_TILE), (unsigned)P);
-  {
-    Timed t(c, KID_DENSE_CLAIM);
-    hipLaunchKernelGGL((gpc::k_dense_claim<CORR>), dim3((unsigned)(nb < 4096 ? nb : 4096), P), dim3(DN_THREADS), 0, c->stream,
-                       (const Rec*)d_rec, cap, d_counts, ref, prm->max_cost, W, H, owner);
-  }
-  {
-    Timed t(c, KID_DENSE_PULL);
-    hipLaunchKernelGGL((gpc::k_dense_pull<CORR>), tiles, dim3(DN_THREADS), 0, c->stream, (const Rec*)d_rec, cap, ref,
-                       (const uint32_t*)owner, g, cells, d_value, pn, ps);
-  }
-  if (g.top > DN_TILE_LEVELS) {
-    Timed t(c, KID_DENSE_TOP);
-    hipLaunchKernelGGL((gpc::k_dense_top<C>), dim3(P), dim3(DN_THREADS), 0, c->stream, g, cells, pn, ps);
-  }
-  {
-    Timed t(c, KID_DENSE_PUSH);
-    hipLaunchKernelGGL((gpc::k_dense_push<C>), tiles, dim3(DN_THREADS), 0, c->stream, g, cells, (const int32_t*)pn,
-                       (const int64_t*)ps, d_value, d_level);
-  }
-  for (int k = KID_DENSE_CLAIM; k <= KID_DENSE_PUSH; ++k)  // (claim and pull are typed by the record, top and push by the channels)
-    snprintf(c->launch_name[k], sizeof c->launch_name[0], "gpc::%s<%s>", kKernelNames[k],
-             k <= KID_DENSE_PULL ? (CORR ? "true" : "false") : (CORR ? "2" : "1"));
-  HIPCHK(c, hipGetLastError());
-  return GPC_OK;
-}
-}  // extern "C++"
-
-int gpc_hip_densify_supports_device(gpc_hip_ctx* c, const gpc_support* d_rec, int cap_per_pair, const int32_t* d_counts,
-                                    const gpc_refinement* d_ref, int W, int H, int npairs, const gpc_densify* prm, int32_t* d_value,
-                                    uint8_t* d_level) {
-  CHK(dense_args(c, d_rec, cap_per_pair, d_counts, d_ref, W, H, npairs, prm, d_value));
-  HIPCHK(c, hipSetDevice(c->device));
-  return dense_fill<false>(c, d_rec, cap_per_pair, d_counts, d_ref, W, H, npairs, prm, d_value, d_level);
-}
-
-int gpc_hip_densify_correspondences_device(gpc_hip_ctx* c, const gpc_correspondence* d_rec, int cap_per_pair, const int32_t* d_counts,
-                                           const gpc_refinement* d_ref, int W, int H, int npairs, const gpc_densify* prm,
-                                           int32_t* d_value, uint8_t* d_level) {
-  CHK(dense_args(c, d_rec, cap_per_pair, d_counts, d_ref, W, H, npairs, prm, d_value));
-  HIPCHK(c, hipSetDevice(c->device));
-  return dense_fill<true>(c, d_rec, cap_per_pair, d_counts, d_ref, W, H, npairs, prm, d_value, d_level);
-}
-
-// match, refine (radius >= 1) and fill, images as all_records takes them
-static int dense_match(gpc_hip_ctx* c, const uint8_t* d_a, const uint8_t* d_b, int W, int H, int npairs, const gpc_settings* s,
-                       int radius, const gpc_densify* prm, int32_t* d_value, uint8_t* d_level, int32_t* d_counts, int32_t* d_ncand) {
-  if (radius < 0 || radius > RF_MAX_RADIUS) return GPC_E_INVALID;
-  CHK(gpc::dn_params(prm, radius >= 1));
-  AllRecords r;
-  CHK(all_records_cap(c, s, W, H, !d_b, &r.cap));
-  CHK(gpc::dn_limits(W, H, npairs, r.cap));  // (before any workspace is made, too)
-  CHK(all_records(c, d_a, d_b, W, H, npairs, s, d_ncand, &r));
-  if (d_counts) HIPCHK(c, hipMemcpyAsync(d_counts, r.counts, sizeof(int32_t) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
-  gpc_refinement* d_ref = nullptr;
-  if (radius >= 1) {
-    CHK(ensure(c, c->dn_ref, sizeof(gpc_refinement) * (size_t)r.cap * npairs));
-    d_ref = (gpc_refinement*)c->dn_ref.p;
-    const uint8_t* d_next = d_b ? d_b : d_a + (size_t)W * H;
-    CHK(d_b ? refine_records<false>(c, r.rec, r.cap, r.counts, d_a, d_next, W, H, npairs, radius, d_ref, nullptr)
-            : refine_records<true>(c, r.rec, r.cap, r.counts, d_a, d_next, W, H, npairs, radius, d_ref, nullptr));
-  }
-  return d_b ? dense_fill<false>(c, r.rec, r.cap, r.counts, d_ref, W, H, npairs, prm, d_value, d_level)
-             : dense_fill<true>(c, r.rec, r.cap, r.counts, d_ref, W, H, npairs, prm, d_value, d_level);
-}
-
-int gpc_hip_densify_batch_device(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H, int npairs,
-                                 const gpc_settings* s, int refine_radius, const gpc_densify* prm, int32_t* d_value, uint8_t* d_level,
-                                 int32_t* d_counts, int32_t* d_ncand) {
-  if (!c || !d_rawL || !d_rawR || !d_value || npairs <= 0) return GPC_E_INVALID;
-  return dense_match(c, d_rawL, d_rawR, W, H, npairs, s, refine_radius, prm, d_value, d_level, d_counts, d_ncand);
-}
-
-int gpc_hip_densify_sequence_device(gpc_hip_ctx* c, const uint8_t* d_frames, int W, int H, int nframes, const gpc_settings* s,
-                                    int refine_radius, const gpc_densify* prm, int32_t* d_value, uint8_t* d_level, int32_t* d_counts,
-                                    int32_t* d_ncand) {
-  if (!c || !d_frames || !d_value || nframes < 2) return GPC_E_INVALID;
-  return dense_match(c, d_frames, nullptr, W, H, nframes - 1, s, refine_radius, prm, d_value, d_level, d_counts, d_ncand);
-}
-
-// Host forms (Stage): chunks of at most 16 pairs -- their records as far as their counts go, their counts, their refinements.
-extern "C++" {
-template <bool CORR>
-static int dense_host(gpc_hip_ctx* c, const void* rec, int cap, const int32_t* counts, const gpc_refinement* ref, int W, int H,
-                      int npairs, const gpc_densify* prm, int32_t* value, uint8_t* level) {
-  const size_t esz = sizeof(gpc::ConsRec<CORR>), C = CORR ? 2 : 1;
-  CHK(dense_args(c, rec, cap, counts, ref, W, H, npairs, prm, value));
-  CHK(host_call_begin(c));
-  const int K = npairs < 16 ? npairs : 16;
-  const size_t n = (size_t)W * H;
-  Stage st(c);
-  const size_t r_rec = st.in(esz * (size_t)cap * K), r_cnt = st.in(sizeof(int32_t) * (size_t)K);
-  const size_t r_ref = st.in(ref ? sizeof(gpc_refinement) * (size_t)cap * K : 0);
-  const size_t r_val = st.out(sizeof(int32_t) * C * n * K), r_lev = st.out(level ? n * K : 0);
-  CHK(st.alloc(0));
-  for (int p0 = 0; p0 < npairs; p0 += K) {
-    const int pc = npairs - p0 < K ? npairs - p0 : K;
-    CHK(st.up(r_cnt, counts + p0, sizeof(int32_t) * (size_t)pc));
-    CHK(st.up_records(r_rec, rec, esz, cap, counts, p0, pc));
-    if (ref) CHK(st.up_records(r_ref, ref, sizeof(gpc_refinement), cap, counts, p0, pc));
-    CHK(dense_fill<CORR>(c, st.p(r_rec), cap, (const int32_t*)st.p(r_cnt), ref ? (const gpc_refinement*)st.p(r_ref) : nullptr, W, H, pc,
-                         prm, (int32_t*)st.p(r_val), level ? st.p(r_lev) : nullptr));
-    CHK(st.down(value + C * n * (size_t)p0, r_val, sizeof(int32_t) * C * n * pc));
-    if (level) CHK(st.down(level + n * (size_t)p0, r_lev, n * pc));
-    CHK(st.wait());
-  }
-  return check_join_err(c);
-}
-}  // extern "C++"
-
-int gpc_hip_densify_supports(gpc_hip_ctx* c, const gpc_support* rec, int cap_per_pair, const int32_t* counts, const gpc_refinement* ref,
-                             int W, int H, int npairs, const gpc_densify* prm, int32_t* value, uint8_t* level) {
-  return dense_host<false>(c, rec, cap_per_pair, counts, ref, W, H, npairs, prm, value, level);
-}
-
-int gpc_hip_densify_correspondences(gpc_hip_ctx* c, const gpc_correspondence* rec, int cap_per_pair, const int32_t* counts,
-                                    const gpc_refinement* ref, int W, int H, int npairs, const gpc_densify* prm, int32_t* value,
-                                    uint8_t* level) {
-  return dense_host<true>(c, rec, cap_per_pair, counts, ref, W, H, npairs, prm, value, level);
-}
+extern "C" {
 
 int gpc_hip_match_batch_device_packed(gpc_hip_ctx* c, const uint8_t* d_rawL, const uint8_t* d_rawR, int W, int H,
                                       int npairs, const gpc_settings* s, uint32_t* d_packed, int cap_per_pair,
@@ -5013,20 +4132,6 @@ int gpc_hip_expand_packed(const uint32_t* packed, const int32_t* rows, int H, in
   expand_rows(packed, rows, GPC_R, H - GPC_R, 0, n, out);
   return GPC_OK;
 }
-
-// Host buffers in, supports out, for the epipolar sort-matcher (the reference's sparsematch settings): results
-// cross the link PACKED (4 bytes per support + the row counts instead of 12 bytes per support) and worker threads
-// expand them into the caller's ndb::Support arrays while the next chunks are uploaded, matched and downloaded.
-// Per chunk k:  upload (s_in) -> kernels (stream) -> counts (s_cnt) | download of k-1 (s_out) | expansion of k-2 (pool).
-// Device results rotate through 3 slots, the page-locked landing area through 4.
-// ph != null: the results are LEFT packed in the caller's arrays (gpc_hip_match_batch_packed) instead of being expanded into `out`
-struct PackedHost {
-  uint32_t* packed;  // [npairs][cap] words xL | xR << 16
-  int32_t* rows;     // [npairs][H] supports per row
-};
-static int match_batch_packed(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, int W, int H, int npairs,
-                              const gpc_settings* s, gpc_support* out, int cap, int32_t* counts, int32_t* ncand,
-                              const PackedHost* ph = nullptr);
 
 // One pair or two, page-locked `out` (BASELINE configs[1] taken literally: the reference's timed region for ONE pair).
 // The chunk pipeline of match_batch_packed is built for the link's throughput: three streams, events, packed records
@@ -5089,43 +4194,19 @@ static int match_batch_direct(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t
   return status;
 }
 
-int gpc_hip_fed_calls(const gpc_hip_ctx* c) { return c ? c->fed_calls : 0; }
-
-int gpc_hip_match_pair_begin(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, int W, int H, const gpc_settings* s);
-
-int gpc_hip_match_batch(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, int W, int H, int npairs,
-                        const gpc_settings* s, gpc_support* out, int cap, int32_t* counts, int32_t* ncand) {
-  if (c && c->ngroups > 1) return GPC_E_UNSUPPORTED;
-  // One pair into a pageable array: the two-step form (results packed over the link, expanded by the workers): 0.20 ms
-  // where the chunk pipeline's machinery took 0.27.  (A page-locked array is written by the kernels themselves: below.)
-  if (c && npairs == 1 && rawL && rawR && out && counts && cap > 0 && s && !device_view_of_host(out)) {
-    CHK(gpc_hip_match_pair_begin(c, rawL, rawR, W, H, s));
-    int n = 0, nl = 0, nr = 0;
-    const int st1 = match_fetch(c, out, cap, &n, &nl, &nr);
-    c->pend.active = false;
-    counts[0] = n;
-    if (ncand) { ncand[0] = nl; ncand[1] = nr; }
-    return st1;
-  }
-  const int st = on_gpu_node(c, npairs, [&] { return match_batch_packed(c, rawL, rawR, W, H, npairs, s, out, cap, counts, ncand); });
-  if (c && st != GPC_OK && st != GPC_E_CAPACITY && st != GPC_E_INVALID) {
-    // An error left the chunk pipeline half way: expansion jobs may still write into `out`, copies may still
-    // target the staging slots.  Nothing of this call may be in flight when the caller gets its buffers back.
-    c->pool.wait_all();
-    if (c->s_in) {
-      (void)hipStreamSynchronize(c->s_in);
-      (void)hipStreamSynchronize(c->s_out);
-      (void)hipStreamSynchronize(c->s_cnt);
-    }
-    if (c->s_aux) (void)hipStreamSynchronize(c->s_aux);
-    (void)hipStreamSynchronize(c->stream);
-  }
-  return st;
-}
-
+// Host buffers in, supports out, for the epipolar sort-matcher (the reference's sparsematch settings): results
+// cross the link PACKED (4 bytes per support + the row counts instead of 12 bytes per support) and worker threads
+// expand them into the caller's ndb::Support arrays while the next chunks are uploaded, matched and downloaded.
+// Per chunk k:  upload (s_in) -> kernels (stream) -> counts (s_cnt) | download of k-1 (s_out) | expansion of k-2 (pool).
+// Device results rotate through 3 slots, the page-locked landing area through 4.
+// ph != null: the results are LEFT packed in the caller's arrays (gpc_hip_match_batch_packed) instead of being expanded into `out`
+struct PackedHost {
+  uint32_t* packed;  // [npairs][cap] words xL | xR << 16
+  int32_t* rows;     // [npairs][H] supports per row
+};
 static int match_batch_packed(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, int W, int H, int npairs,
                               const gpc_settings* s, gpc_support* out, int cap, int32_t* counts, int32_t* ncand,
-                              const PackedHost* ph) {
+                              const PackedHost* ph = nullptr) {
   if (!c || !rawL || !rawR || (!out && !ph) || !counts || npairs <= 0 || cap <= 0) return GPC_E_INVALID;
   if (ph && (!ph->packed || !ph->rows)) return GPC_E_INVALID;
   const double t_entry = host_ms();
@@ -5337,6 +4418,38 @@ static int match_batch_packed(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t
   CHK(check_join_err(c));
   c->stage_ms[3] = (float)(host_ms() - t_entry);
   return status;
+}
+
+int gpc_hip_fed_calls(const gpc_hip_ctx* c) { return c ? c->fed_calls : 0; }
+
+int gpc_hip_match_batch(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, int W, int H, int npairs,
+                        const gpc_settings* s, gpc_support* out, int cap, int32_t* counts, int32_t* ncand) {
+  if (c && c->ngroups > 1) return GPC_E_UNSUPPORTED;
+  // One pair into a pageable array: the two-step form (results packed over the link, expanded by the workers): 0.20 ms
+  // where the chunk pipeline's machinery took 0.27.  (A page-locked array is written by the kernels themselves: below.)
+  if (c && npairs == 1 && rawL && rawR && out && counts && cap > 0 && s && !device_view_of_host(out)) {
+    CHK(gpc_hip_match_pair_begin(c, rawL, rawR, W, H, s));
+    int n = 0, nl = 0, nr = 0;
+    const int st1 = match_fetch(c, out, cap, &n, &nl, &nr);
+    c->pend.active = false;
+    counts[0] = n;
+    if (ncand) { ncand[0] = nl; ncand[1] = nr; }
+    return st1;
+  }
+  const int st = on_gpu_node(c, npairs, [&] { return match_batch_packed(c, rawL, rawR, W, H, npairs, s, out, cap, counts, ncand); });
+  if (c && st != GPC_OK && st != GPC_E_CAPACITY && st != GPC_E_INVALID) {
+    // An error left the chunk pipeline half way: expansion jobs may still write into `out`, copies may still
+    // target the staging slots.  Nothing of this call may be in flight when the caller gets its buffers back.
+    c->pool.wait_all();
+    if (c->s_in) {
+      (void)hipStreamSynchronize(c->s_in);
+      (void)hipStreamSynchronize(c->s_out);
+      (void)hipStreamSynchronize(c->s_cnt);
+    }
+    if (c->s_aux) (void)hipStreamSynchronize(c->s_aux);
+    (void)hipStreamSynchronize(c->stream);
+  }
+  return st;
 }
 
 int gpc_hip_match_batch_packed(gpc_hip_ctx* c, const uint8_t* rawL, const uint8_t* rawR, int W, int H, int npairs,

@@ -43,11 +43,23 @@ def test_every_variable_the_library_reads_is_in_the_table_and_nothing_else_is():
 
 
 def test_knobs_are_read_at_context_creation_not_per_launch():
-    """(round-4 advice) no getenv on a launch path: inside gpc_hip.hip every getenv sits in gpc_hip_create or in one of
-    the once-per-context helpers it calls."""
-    text = open(os.path.join(ROOT, "opengpc_amd", "csrc", "gpc_hip.hip")).read()
+    """(round-4 advice) no getenv on a launch path: in every file of opengpc_amd/csrc every getenv sits in gpc_hip_create or in
+    one of the once-per-context helpers it calls."""
+    csrc = os.path.join(ROOT, "opengpc_amd", "csrc")
     allowed = ("int gpc_hip_create(", "void find_gpu_node_cpus(", "int default_expand_threads(")
-    starts = sorted((m.start(), m.group(0)) for m in re.finditer(r"^(?:static |inline )?(?:[\w:<>*&]+ )+\w+\([^;{]*\)\s*(?:const\s*)?\{", text, re.M))
-    for m in re.finditer(r'getenv\("', text):
-        owner = [s for s in starts if s[0] < m.start()][-1][1]
-        assert any(a in owner.replace("\n", " ") for a in allowed), owner
+    seen, reads = set(), 0
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".h", ".hip")):
+            continue
+        text = open(os.path.join(csrc, f), errors="replace").read()
+        starts = sorted((m.start(), m.group(0)) for m in re.finditer(r"^(?:static |inline )?(?:[\w:<>*&]+ )+\w+\([^;{]*\)\s*(?:const\s*)?\{", text, re.M))
+        seen.update(a for a in allowed for _, s in starts if a in s.replace("\n", " "))
+        for m in re.finditer(r'getenv\("', text):
+            before = [s for s in starts if s[0] < m.start()]
+            assert before, "%s: a getenv outside every function, line %d" % (f, text.count("\n", 0, m.start()) + 1)
+            owner = before[-1][1]
+            assert any(a in owner.replace("\n", " ") for a in allowed), (f, owner)
+            reads += 1
+    # (a function that moved or was renamed must not leave the scan with nothing to hold)
+    assert reads >= 1
+    assert seen == set(allowed), sorted(set(allowed) - seen)

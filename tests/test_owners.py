@@ -1,5 +1,5 @@
 """Who frees what: the owner types of opengpc_amd/csrc/owners.h driven by a stand-alone program with a recording
-backend under AddressSanitizer and UBSan, and a source check that gpc_hip.hip releases nothing by hand."""
+backend under AddressSanitizer and UBSan, and a source check that the host code releases nothing by hand."""
 import os
 import re
 import subprocess
@@ -30,18 +30,25 @@ def test_owners_header_is_host_only():
 
 def test_nothing_is_released_by_hand():
     """hipFree, hipHostFree, hipStreamDestroy and hipEventDestroy are called by the owners' HIP backends (the structs DevMem,
-    PinnedMem, StreamApi, EventApi) and by gpc_hip_host_free, which frees what the caller owns -- nowhere else"""
-    text = open(os.path.join(CSRC, "gpc_hip.hip")).read()
+    PinnedMem, StreamApi, EventApi) and by gpc_hip_host_free, which frees what the caller owns -- nowhere else in
+    opengpc_amd/csrc, whichever file holds them (owners.h names the calls in prose only: no hit there)"""
+    texts = {f: open(os.path.join(CSRC, f), errors="replace").read() for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".hip"))}
     allowed = {"hipFree(": "DevMem", "hipHostFree(": "PinnedMem", "hipStreamDestroy(": "StreamApi", "hipEventDestroy(": "EventApi"}
-    # the body each call may stand in: from the opening line of the struct / function to the first line that is just a brace
-    def body(opening):
-        at = text.index(opening)
-        return at, at + re.search(r"^\};?$", text[at:], flags=re.M).end()
+    # the bodies each call may stand in, per file: from the opening line of the struct / function to the first line that is
+    # just a brace
+    def bodies(text, opening):
+        out = []
+        for m in re.finditer(r"^" + re.escape(opening), text, flags=re.M):
+            out.append((m.start(), m.start() + re.search(r"^\};?$", text[m.start():], flags=re.M).end()))
+        return out
     for call, backend in allowed.items():
-        spans = [body("struct %s {" % backend)]
-        if call == "hipHostFree(":
-            spans.append(body("int gpc_hip_host_free("))
-        hits = [m.start() for m in re.finditer(r"\b" + re.escape(call), text)]
-        assert hits, call
-        for h in hits:
-            assert any(a <= h < b for a, b in spans), "%s at line %d" % (call, text.count("\n", 0, h) + 1)
+        found = 0
+        for f, text in texts.items():
+            spans = bodies(text, "struct %s {" % backend)
+            if call == "hipHostFree(":
+                spans += bodies(text, "int gpc_hip_host_free(")
+            for m in re.finditer(r"\b" + re.escape(call), text):
+                h = m.start()
+                assert any(a <= h < b for a, b in spans), "%s at %s:%d" % (call, f, text.count("\n", 0, h) + 1)
+                found += 1
+        assert found, call
