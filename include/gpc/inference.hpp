@@ -50,6 +50,9 @@ namespace tracking {  // gpc/tracking.hpp (extension: point tracks over a frame 
 struct Track;
 class TrackStream;
 }  // namespace tracking
+namespace quads {  // gpc/quads.hpp (extension: circular matches of a stereo sequence closed into quads)
+struct Quad;
+}  // namespace quads
 namespace inference {
 
 typedef std::chrono::high_resolution_clock::time_point time_point;
@@ -279,6 +282,15 @@ class Forest {
   // into point tracks on the device (gpc_hip_track_sequence); the tracks of at least minLength records, in track-id order.
   std::vector<tracking::Track> trackSequence(std::vector<ndb::Buffer<uint8_t>>& frames, FilterMask& fm,
                                              InferenceSettings settings, int minLength = 1);
+
+  // Extension (gpc/quads.hpp, which defines it): a stereo sequence matched three ways from one hashing of its 2 N images --
+  // supports of (L_t, R_t), correspondences of (L_t, L_t+1) and (R_t, R_t+1) -- and the circular matches closed into quads
+  // on the device (gpc_hip_quads_sequence); result[t] holds the quads of frames t and t + 1.  The two settings must share
+  // gradientThreshold_.
+  std::vector<std::vector<quads::Quad>> stereoSequenceQuads(std::vector<ndb::Buffer<uint8_t>>& leftFrames,
+                                                            std::vector<ndb::Buffer<uint8_t>>& rightFrames, FilterMask& fm,
+                                                            InferenceSettings stereoSettings, InferenceSettings flowSettings,
+                                                            int tol = 1);
 
   // the warm-up of readForest for a group-mode forest (gpc_hip_warmup with the groups set)
   void warmUp(std::vector<FilterMask>& groups) {

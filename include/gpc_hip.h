@@ -972,6 +972,95 @@ int gpc_hip_densify_correspondences(gpc_hip_ctx* ctx, const gpc_correspondence* 
                                     const gpc_refinement* ref, int width, int height, int npairs, const gpc_densify* prm,
                                     int32_t* value, uint8_t* level);
 
+/* ---- stereo sequences: circular matches closed into quads ----------------------------- */
+/* A stereo video is where both kinds of match apply: the supports of (L_t, R_t) and the correspondences of (L_t, L_t+1)
+ * and (R_t, R_t+1).  The circular match L_t -> R_t -> R_t+1 -> L_t+1 -> L_t joins them by pixel position; it is the
+ * strongest outlier filter a stereo rig gives for free, and what it keeps is a sparse scene-flow record: position,
+ * disparity before, image motion, disparity after.  The reference has no counterpart: it matches one pair
+ * (Forest::stereoMatch, inference.hpp:344-361) and leaves every use of two results to its caller.  The rule is therefore
+ * this library's own; it is made of integers only, so that every implementation of it gives the same bytes.
+ *
+ * N = nframes stereo frames, P = N - 1 steps, images of width x height, a pixel's index y * width + x.  Inputs: per frame
+ * t the supports S[t][0 .. ms_t) of (L_t, R_t), ms_t = min(max(nsup[t], 0), cap_s); per step t FL[t][0 .. mfl_t) of
+ * (L_t, L_t+1) and FR[t][0 .. mfr_t) of (R_t, R_t+1), clipped to cap_f in the same way.
+ *   A support takes part when 0 <= x < width, 0 <= y < height, d is finite and integral with |d| <= 16384 (tested before
+ *     d is converted, so that no conversion is undefined) and 0 <= x - (int)d < width.  Its left pixel is (x, y), its
+ *     right pixel (x - d, y).  A flow record takes part when its source and its target lie inside the image.
+ *   Lookup: first_S[t](p) is the lowest i that takes part and whose left pixel is p; first_FL[t](p) and first_FR[t](p) the
+ *     lowest j that takes part and whose source pixel is p; "none" where there is no such record.
+ *   Start: support i of S[t], t < P, when it takes part and i == first_S[t](its left pixel).
+ *   Closing, for a start i with left pixel a, right pixel b and disparity d: j = first_FL[t](a) and k = first_FR[t](b) must
+ *     both exist; a' = the target of FL[t][j], b' = the target of FR[t][k]; i' = first_S[t+1](a') must exist, with disparity
+ *     d'; c' = (a'.x - d', a'.y); the circle closes when |c'.x - b'.x| <= tol and |c'.y - b'.y| <= tol.
+ *   Settle: among the starts of step t that close on the same i' the lowest i keeps its quad -- the lowest index is the one
+ *     choice that does not depend on which thread arrives first.  So every support of frame t + 1 ends at most one quad of
+ *     step t and starts at most one of step t + 1: a consumer chains quads by support1 == support0 of the next step.
+ *   Output: the quads of step t by i ascending in quads[t][0 .. min(nq_t, quad_cap)); nquads[t] = nq_t is the true count;
+ *     nothing is written behind a step's valid quads.  quad_cap = 0 is allowed, and quads may then be NULL.
+ * 0 <= tol <= 255, nframes >= 2, cap_s, cap_f > 0, quad_cap >= 0: GPC_E_INVALID otherwise.  nframes * cap_s,
+ * (nframes - 1) * cap_f and (nframes - 1) * quad_cap must not exceed 2^31 - 1, width * height 2^30 and nframes 65535
+ * (GPC_E_UNSUPPORTED). */
+typedef struct gpc_quad {
+  int32_t x, y;     /* a: the point in L_t; in R_t it is (x - d0, y)                                   */
+  int32_t d0;       /* d: the disparity at t                                                           */
+  int32_t u, v;     /* a' - a: the point in L_t+1 is (x + u, y + v), in R_t+1 (x + u - d1, y + v)       */
+  int32_t d1;       /* d': the disparity at t + 1                                                      */
+  int32_t support0; /* i:  the start's index in S[t]                                                   */
+  int32_t support1; /* i': the index in S[t + 1] the circle closes on                                  */
+} gpc_quad;
+/* Records already on the device, in the layouts gpc_hip_match_batch_device (d_sup [N][cap_s], d_nsup[N]) and
+ * gpc_hip_match_sequence_device (d_flowL, d_flowR [P][cap_f], d_nflowL, d_nflowR [P]) write; d_quads [P][quad_cap],
+ * d_nquads[P].  No forest is needed; the counts are read on the device, and the call only queues work on the context's
+ * stream (six launches per group of steps: fill the per-pixel planes, scatter the record indices, close, settle and
+ * count, scan, write); read the outputs after gpc_hip_synchronize or another wait on the stream.  Workspaces of the
+ * context, grown on demand, for a group of g steps: 4 bytes per pixel for each of 3 g + 1 planes, 8 bytes per support slot
+ * of g frames (plus 4 bytes per 2048 of them).  g is all P steps where that stays within 1 GiB of planes, else the
+ * largest number of steps that does (at least one): the steps then go through the launches in groups, with the same
+ * result. */
+int gpc_hip_quads_records_device(gpc_hip_ctx* ctx, const gpc_support* d_sup, int cap_s, const int32_t* d_nsup,
+                                 const gpc_correspondence* d_flowL, const gpc_correspondence* d_flowR, int cap_f,
+                                 const int32_t* d_nflowL, const int32_t* d_nflowR, int width, int height, int nframes, int tol,
+                                 gpc_quad* d_quads, int quad_cap, int32_t* d_nquads);
+/* The three record sets of a stereo sequence from ONE k_preprocess and ONE k_hash launch over its 2 N images (d_left,
+ * d_right: [N][height][width] each): exactly what gpc_hip_match_batch_device(d_left, d_right, stereo_settings),
+ * gpc_hip_match_sequence_device(d_left, flow_settings) and gpc_hip_match_sequence_device(d_right, flow_settings) write, in
+ * that order, with any matcher setting on either side and either arithmetic.  d_ncand[2][N] (optional): the candidates of
+ * the left frames, then of the right frames.  The two settings must share gradient_threshold (GPC_E_INVALID otherwise).
+ * Group mode: GPC_E_UNSUPPORTED; no forest: GPC_E_NO_FOREST; with two lanes (gpc_hip_set_pipeline(ctx, 2)) the lanes are
+ * drained and the call runs on the context's stream.  Waiting is as gpc_hip_match_batch_device and
+ * gpc_hip_match_sequence_device document it.  The images are hashed in the batch's order [t][side]; each side's code
+ * images are then copied on the device into a block of their own (4 bytes per pixel and image held twice), which the flow
+ * joins read as a sequence's frames. */
+int gpc_hip_match_stereo_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int width, int height,
+                                         int nframes, const gpc_settings* stereo_settings, const gpc_settings* flow_settings,
+                                         gpc_support* d_sup, int cap_s, int32_t* d_nsup, gpc_correspondence* d_flowL,
+                                         gpc_correspondence* d_flowR, int cap_f, int32_t* d_nflowL, int32_t* d_nflowR,
+                                         int32_t* d_ncand);
+/* gpc_hip_match_stereo_sequence_device, then gpc_hip_quads_records_device over what it wrote: all outputs of both. */
+int gpc_hip_quads_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int width, int height,
+                                  int nframes, const gpc_settings* stereo_settings, const gpc_settings* flow_settings, int tol,
+                                  gpc_support* d_sup, int cap_s, int32_t* d_nsup, gpc_correspondence* d_flowL,
+                                  gpc_correspondence* d_flowR, int cap_f, int32_t* d_nflowL, int32_t* d_nflowR, int32_t* d_ncand,
+                                  gpc_quad* d_quads, int quad_cap, int32_t* d_nquads);
+/* The same from / to host memory (pageable or page-locked), synchronous.  GPC_E_CAPACITY when any count exceeds its
+ * capacity (a frame's supports cap_s, a step's correspondences cap_f, a step's quads quad_cap); what is written is then as
+ * defined above.  gpc_hip_quads_records needs no forest and sends each list's first m records only.  A quad joins records
+ * of two frames and three lists, so neither form is cut into chunks: the whole call is staged on the device and the
+ * device form runs once.  The calls are therefore BOUNDED BY DEVICE MEMORY: they hold
+ *   N * cap_s * 12  +  2 * P * cap_f * 16  +  P * quad_cap * 32   bytes of staging (the sequence form 2 * N * W * H more;
+ *   the counts and the padding of each block to 16 bytes are not counted),
+ *   the closing workspace stated at gpc_hip_quads_records_device, and (the sequence form) what the matchers keep for 2 N
+ *   images: smoothed image, gradient image and codes, 6 bytes per pixel and image, 4 more for each side's copy of the
+ *   codes, plus the chosen matchers' own workspaces. */
+int gpc_hip_quads_records(gpc_hip_ctx* ctx, const gpc_support* sup, int cap_s, const int32_t* nsup,
+                          const gpc_correspondence* flowL, const gpc_correspondence* flowR, int cap_f, const int32_t* nflowL,
+                          const int32_t* nflowR, int width, int height, int nframes, int tol, gpc_quad* quads, int quad_cap,
+                          int32_t* nquads);
+int gpc_hip_quads_sequence(gpc_hip_ctx* ctx, const uint8_t* left, const uint8_t* right, int width, int height, int nframes,
+                           const gpc_settings* stereo_settings, const gpc_settings* flow_settings, int tol, gpc_support* sup,
+                           int cap_s, int32_t* nsup, gpc_correspondence* flowL, gpc_correspondence* flowR, int cap_f,
+                           int32_t* nflowL, int32_t* nflowR, int32_t* ncand, gpc_quad* quads, int quad_cap, int32_t* nquads);
+
 /* ---- measurement -------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the context's stream.  When enabled every launch of
  * the named kernels is bracketed by hipEvents; gpc_hip_kernel_time returns the summed
@@ -980,7 +1069,7 @@ int gpc_hip_enable_kernel_timing(gpc_hip_ctx* ctx, int enable);
 /* Restrict the bracketing to the kernels whose index bit is set (default: all).  Every pair of
  * event records costs a little stream time, so a benchmark times only the kernel it reports.  The mask has 32 bits and
  * gpc_hip_kernel_count() is the number of slots it addresses (at most 32).  gpc_hip_kernel_slots() counts every slot:
- * those from gpc_hip_kernel_count() on (k_refine, k_pyr_*, k_dense_*) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
+ * those from gpc_hip_kernel_count() on (k_refine, k_pyr_*, k_dense_*, k_tf_*, k_quad_*) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
  * gpc_hip_kernel_launch_name and gpc_hip_kernel_time take their indices like any other. */
 int gpc_hip_set_kernel_timing_mask(gpc_hip_ctx* ctx, unsigned mask);
 int gpc_hip_reset_kernel_timing(gpc_hip_ctx* ctx);

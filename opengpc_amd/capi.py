@@ -31,6 +31,9 @@ SCORE_DTYPE = np.dtype([("n_records", "<i8"), ("n_ignored", "<i8"), ("n_no_truth
 TRACK_DTYPE = np.dtype([("first_pair", "<i4"), ("first_record", "<i4"), ("length", "<i4"), ("last_record", "<i4")])
 # gpc_refinement: one per record (gpc_hip_refine_*); flags bit 0 evaluated, bit 1 minimum in x, bit 2 minimum in y
 REFINEMENT_DTYPE = np.dtype([("dx_q8", "<i2"), ("dy_q8", "<i2"), ("cost", "<u2"), ("flags", "<u2")])
+# gpc_quad: one closed circular match of a stereo sequence (gpc_hip_quads_*)
+QUAD_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("d0", "<i4"), ("u", "<i4"), ("v", "<i4"), ("d1", "<i4"), ("support0", "<i4"),
+                       ("support1", "<i4")])
 
 
 class Settings(C.Structure):
@@ -134,6 +137,8 @@ SYMBOLS = [
     "gpc_hip_pyramid_batch", "gpc_hip_pyramid_sequence",
     "gpc_hip_densify_supports_device", "gpc_hip_densify_correspondences_device", "gpc_hip_densify_batch_device",
     "gpc_hip_densify_sequence_device", "gpc_hip_densify_supports", "gpc_hip_densify_correspondences",
+    "gpc_hip_quads_records_device", "gpc_hip_match_stereo_sequence_device", "gpc_hip_quads_sequence_device",
+    "gpc_hip_quads_records", "gpc_hip_quads_sequence",
 ]
 
 
@@ -296,6 +301,13 @@ def load():
     L.gpc_hip_extract_triplets.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
     L.gpc_hip_extract_triplets_device.argtypes = L.gpc_hip_extract_triplets.argtypes
     L.gpc_hip_train_set_read.argtypes = [vp, vp, ci, ci, vp]
+    L.gpc_hip_quads_records_device.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, vp, ci, vp]
+    L.gpc_hip_quads_records.argtypes = L.gpc_hip_quads_records_device.argtypes
+    L.gpc_hip_match_stereo_sequence_device.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(Settings), C.POINTER(Settings), vp, ci, vp, vp,
+                                                       vp, ci, vp, vp, vp]
+    L.gpc_hip_quads_sequence_device.argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(Settings), C.POINTER(Settings), ci, vp, ci, vp, vp,
+                                                vp, ci, vp, vp, vp, vp, ci, vp]
+    L.gpc_hip_quads_sequence.argtypes = L.gpc_hip_quads_sequence_device.argtypes
     L.gpc_hip_debug_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
     return L
@@ -1151,6 +1163,78 @@ class Context:
         fn = self.L.gpc_hip_densify_correspondences if corr else self.L.gpc_hip_densify_supports
         self._ck(fn(self.h, _ptr(records), cap, _ptr(counts), _ptr(ref), width, height, P, C.byref(prm), _ptr(value), _ptr(level)))
         return value, level
+
+    # ---- stereo sequences (gpc_hip_quads_*): circular matches closed into quads on the device
+    def quads_records_device(self, d_sup, cap_s, d_nsup, d_flowL, d_flowR, cap_f, d_nflowL, d_nflowR, width, height, nframes, tol,
+                             d_quads, quad_cap, d_nquads):
+        """Device pointers: d_sup [N][cap_s] of SUPPORT_DTYPE, d_nsup [N], d_flowL / d_flowR [N-1][cap_f] of CORR_DTYPE, their
+        counts [N-1], d_quads [N-1][quad_cap] of QUAD_DTYPE, d_nquads [N-1] int32; asynchronous, no forest needed."""
+        self._ck(self.L.gpc_hip_quads_records_device(self.h, d_sup, int(cap_s), d_nsup, d_flowL, d_flowR, int(cap_f), d_nflowL,
+                                                     d_nflowR, int(width), int(height), int(nframes), int(tol), d_quads or 0,
+                                                     int(quad_cap), d_nquads))
+
+    def match_stereo_sequence_device(self, d_left, d_right, width, height, nframes, stereo_settings, flow_settings, d_sup, cap_s,
+                                     d_nsup, d_flowL, d_flowR, cap_f, d_nflowL, d_nflowR, d_ncand=0):
+        """The supports of (L_t, R_t) and the correspondences of (L_t, L_t+1) and (R_t, R_t+1) from one hashing of the 2 N
+        images (gpc_hip_match_stereo_sequence_device); d_ncand [2][N] optional."""
+        self._ck(self.L.gpc_hip_match_stereo_sequence_device(self.h, d_left, d_right, int(width), int(height), int(nframes),
+                                                             C.byref(stereo_settings), C.byref(flow_settings), d_sup, int(cap_s),
+                                                             d_nsup, d_flowL, d_flowR, int(cap_f), d_nflowL, d_nflowR, d_ncand or 0))
+
+    def quads_sequence_device(self, d_left, d_right, width, height, nframes, stereo_settings, flow_settings, tol, d_sup, cap_s,
+                              d_nsup, d_flowL, d_flowR, cap_f, d_nflowL, d_nflowR, d_ncand, d_quads, quad_cap, d_nquads):
+        """match_stereo_sequence_device, then the closing over what it wrote (gpc_hip_quads_sequence_device)."""
+        self._ck(self.L.gpc_hip_quads_sequence_device(self.h, d_left, d_right, int(width), int(height), int(nframes),
+                                                      C.byref(stereo_settings), C.byref(flow_settings), int(tol), d_sup, int(cap_s),
+                                                      d_nsup, d_flowL, d_flowR, int(cap_f), d_nflowL, d_nflowR, d_ncand or 0,
+                                                      d_quads or 0, int(quad_cap), d_nquads))
+
+    def quads_records(self, sup, nsup, flowL, nflowL, flowR, nflowR, width, height, tol=1, quad_cap=None, quads_out=None):
+        """Host supports [N, cap_s] of SUPPORT_DTYPE with counts [N], correspondences flowL / flowR [N-1, cap_f] of CORR_DTYPE
+        with counts [N-1] -> (quads [N-1, quad_cap] of QUAD_DTYPE, nquads [N-1], status).  Quads beyond min(nquads[t],
+        quad_cap) are left as they were (zero in an array made here).  quad_cap None: cap_s, which always suffices."""
+        sup, flowL, flowR = (a if a.flags.c_contiguous else np.ascontiguousarray(a) for a in map(np.asarray, (sup, flowL, flowR)))
+        if sup.dtype != SUPPORT_DTYPE or sup.ndim != 2 or sup.shape[0] < 2 or sup.shape[1] < 1:
+            raise ValueError("sup: [N, cap_s] of SUPPORT_DTYPE, N >= 2")
+        N, cap_s = sup.shape
+        if flowL.dtype != CORR_DTYPE or flowR.dtype != CORR_DTYPE or flowL.shape != flowR.shape or flowL.ndim != 2 or \
+                flowL.shape[0] != N - 1 or flowL.shape[1] < 1:
+            raise ValueError("flowL, flowR: [N - 1, cap_f] of CORR_DTYPE")
+        cap_f = flowL.shape[1]
+        nsup, nflowL, nflowR = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (nsup, nflowL, nflowR))
+        if len(nsup) != N or len(nflowL) != N - 1 or len(nflowR) != N - 1:
+            raise ValueError("counts: one per frame / step")
+        quad_cap = cap_s if quad_cap is None else int(quad_cap)
+        quads = quads_out if quads_out is not None else np.zeros((N - 1, max(quad_cap, 1)), QUAD_DTYPE)
+        nquads = np.zeros(N - 1, np.int32)
+        st = self.L.gpc_hip_quads_records(self.h, _ptr(sup), cap_s, _ptr(nsup), _ptr(flowL), _ptr(flowR), cap_f, _ptr(nflowL),
+                                          _ptr(nflowR), int(width), int(height), N, int(tol), _ptr(quads), quad_cap, _ptr(nquads))
+        self._ck(st, allow=(E_CAPACITY,))
+        return quads, nquads, st
+
+    def quads_sequence(self, left, right, stereo_settings, flow_settings, tol=1, cap_s=None, cap_f=None, quad_cap=None, alloc=None):
+        """left, right [N, H, W] uint8 -> dict(sup, nsup, flowL, nflowL, flowR, nflowR, ncand [2, N], quads, nquads, status):
+        the three record sets of the stereo sequence and its quads (gpc_hip_quads_sequence).  alloc(shape, dtype): where
+        the output arrays come from (np.zeros; Context.pinned_empty for page-locked ones)."""
+        left, right = _host_frames(left), _host_frames(right)
+        if left.shape != right.shape:
+            raise ValueError("left and right: the same [N, H, W]")
+        N, H, W = left.shape
+        inner = max((W - 26) * (H - 26), 1)
+        cap_s = inner if cap_s is None else int(cap_s)
+        cap_f = inner if cap_f is None else int(cap_f)
+        quad_cap = cap_s if quad_cap is None else int(quad_cap)
+        alloc = alloc or (lambda shape, dtype: np.zeros(shape, dtype))
+        o = dict(sup=alloc((N, cap_s), SUPPORT_DTYPE), nsup=alloc((N,), np.int32), flowL=alloc((N - 1, cap_f), CORR_DTYPE),
+                 nflowL=alloc((N - 1,), np.int32), flowR=alloc((N - 1, cap_f), CORR_DTYPE), nflowR=alloc((N - 1,), np.int32),
+                 ncand=alloc((2, N), np.int32), quads=alloc((N - 1, max(quad_cap, 1)), QUAD_DTYPE), nquads=alloc((N - 1,), np.int32))
+        st = self.L.gpc_hip_quads_sequence(self.h, _ptr(left), _ptr(right), W, H, N, C.byref(stereo_settings), C.byref(flow_settings),
+                                           int(tol), _ptr(o["sup"]), cap_s, _ptr(o["nsup"]), _ptr(o["flowL"]), _ptr(o["flowR"]), cap_f,
+                                           _ptr(o["nflowL"]), _ptr(o["nflowR"]), _ptr(o["ncand"]), _ptr(o["quads"]), quad_cap,
+                                           _ptr(o["nquads"]))
+        self._ck(st, allow=(E_CAPACITY,))
+        o["status"] = st
+        return o
 
     # ---- fern training: the scoring loop
     def train_set(self, triplets):

@@ -39,6 +39,7 @@
 #include "k_partition.h"
 #include "k_preprocess.h"
 #include "k_pyramid.h"
+#include "k_quad.h"
 #include "k_refine.h"
 #include "k_rowjoin.h"
 #include "k_rowjoin_fused.h"
@@ -53,9 +54,9 @@
 #include "pyramid_host.h"
 #include "track_stream_host.h"
 
-// Five sections of the host code below are cut out at their rules into files of their own, csrc/host_*.h, and included where
+// Six sections of the host code below are cut out at their rules into files of their own, csrc/host_*.h, and included where
 // they stood: host_staging.h (what scoring, tracks and the stages after them share), host_consensus.h, host_refine.h,
-// host_pyramid.h and host_dense.h.  They are parts of THIS translation unit, not self-contained headers: each needs what
+// host_pyramid.h, host_dense.h and host_quads.h.  They are parts of THIS translation unit, not self-contained headers: each needs what
 // stands above its include, and `#pragma once` is all the guard it has.  Each says its linkage once: an anonymous namespace
 // with its types, helpers and templates, then one extern "C" block with its entry points.  Everything else is still here.
 
@@ -107,6 +108,13 @@ enum KernelId {
   KID_TF_EVAL,
   KID_TF_TOT,
   KID_TF_COMMIT,
+  KID_QUAD_SIDES,
+  KID_QUAD_FILL,
+  KID_QUAD_SCATTER,
+  KID_QUAD_CLOSE,
+  KID_QUAD_SETTLE,
+  KID_QUAD_SCAN,
+  KID_QUAD_WRITE,
   KID_COUNT
 };
 const char* const kKernelNames[KID_COUNT] = {
@@ -117,7 +125,8 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_trs_fill", "k_trs_scatter", "k_trs_link", "k_trs_settle", "k_trs_scan", "k_trs_walk", "k_trs_save", "k_trs_ncand",
     "k_score_records", "k_score_matchable", "k_refine", "k_pyr_down", "k_pyr_keep", "k_pyr_scan", "k_pyr_write",
     "k_dense_claim", "k_dense_pull", "k_dense_top", "k_dense_push",
-    "k_tf_begin", "k_tf_eval", "k_tf_tot", "k_tf_commit"};
+    "k_tf_begin", "k_tf_eval", "k_tf_tot", "k_tf_commit",
+    "k_quad_sides", "k_quad_fill", "k_quad_scatter", "k_quad_close", "k_quad_settle", "k_quad_scan", "k_quad_write"};
 
 // The owners of owners.h over the HIP runtime.  Everything the library allocates passes through these four backends, which
 // also keep the process-wide counts that gpc_hip_debug_live_resources reports.
@@ -376,6 +385,12 @@ struct gpc_hip_ctx {
   // densifying (gpc_hip_densify_*): the owner plane, the counts and the sums of the cell pyramid, the refinements of the
   // match-and-fill forms
   DevBuf dn_owner, dn_n, dn_s, dn_ref;
+  // quads over a stereo sequence (gpc_hip_quads_*): the per-pixel planes of a group of steps followed by its owner words
+  // (one fill covers both), the candidate i' per support slot, the quad counts per chunk; the image-major copies of the
+  // statistics words, code images and (32-bit codes) candidate bytes of each side, which the two flow joins of
+  // gpc_hip_match_stereo_sequence_device read
+  DevBuf qd_plane, qd_sel, qd_blk, qd_stats, qd_codes[2], qd_gcand[2];
+  int quad_steps = 0;         // GPC_HIP_QUAD_STEPS: steps per group of the closing (tests; default: what QD_PLANE_BYTES holds)
   DevBuf sstats;  // frame sequences: the frames' statistics expanded into the pair layout [npairs*2] (k_seq_stats)
 
   // workspaces
@@ -2255,6 +2270,10 @@ int gpc_hip_create(int device, gpc_hip_ctx** out) {
     const int v = atoi(e);
     if (v >= 2 && v <= 1024) c->seq_frames = v;
   }
+  if (const char* e = getenv("GPC_HIP_QUAD_STEPS")) {
+    const int v = atoi(e);
+    if (v >= 1 && v <= 1024) c->quad_steps = v;
+  }
   const char* et = getenv("GPC_HIP_EXPAND_THREADS");
   if (et && atoi(et) > 0 && atoi(et) <= 64) c->expand_threads = atoi(et);
   if (const char* e = getenv("GPC_HIP_UPLOAD")) c->upload_mode = atoi(e);
@@ -4104,6 +4123,7 @@ int gpc_hip_track_stream_read_tracks(gpc_hip_ctx* c, gpc_hip_track_stream* s, in
 #include "host_refine.h"
 #include "host_pyramid.h"
 #include "host_dense.h"
+#include "host_quads.h"
 
 extern "C" {
 

@@ -121,8 +121,8 @@ __global__ __launch_bounds__(TR_THREADS) void k_track_settle(int cap, const int3
   if (threadIdx.x == 0) blkcnt[(long)t * nchunk + blockIdx.x] = s_n;
 }
 
-// one workgroup: exclusive scan of the N chunk counts in place, the total into *n_tracks
-__global__ __launch_bounds__(1024) void k_track_scan(int32_t* __restrict__ blkcnt, long N, int32_t* __restrict__ n_tracks) {
+// one workgroup (of whole waves, at most 1024 threads): exclusive scan of N counts in place, the total into *n_tracks
+__device__ __forceinline__ void tr_scan_block(int32_t* __restrict__ blkcnt, long N, int32_t* __restrict__ n_tracks) {
   __shared__ int s_w[16];
   __shared__ int s_carry;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -150,6 +150,11 @@ __global__ __launch_bounds__(1024) void k_track_scan(int32_t* __restrict__ blkcn
     __syncthreads();
   }
   if (threadIdx.x == 0) *n_tracks = s_carry;
+}
+
+// one workgroup: exclusive scan of the N chunk counts in place, the total into *n_tracks
+__global__ __launch_bounds__(1024) void k_track_scan(int32_t* __restrict__ blkcnt, long N, int32_t* __restrict__ n_tracks) {
+  tr_scan_block(blkcnt, N, n_tracks);
 }
 
 // grid (nchunk, P): the heads of chunk b of pair t are tracks blkoff[t * nchunk + b] + their rank in record order
