@@ -1061,6 +1061,88 @@ int gpc_hip_quads_sequence(gpc_hip_ctx* ctx, const uint8_t* left, const uint8_t*
                            int cap_s, int32_t* nsup, gpc_correspondence* flowL, gpc_correspondence* flowR, int cap_f,
                            int32_t* nflowL, int32_t* nflowR, int32_t* ncand, gpc_quad* quads, int quad_cap, int32_t* nquads);
 
+/* ---- clean dense fields: cross-check, speckles, median ------------------------------------ */
+/* The fill of gpc_hip_densify_* gives a value to every pixel that has min_count matches somewhere around it: occluded
+ * regions, the halo of a foreground object and the blocks around a single wrong match are filled too.  This stage takes
+ * them out again: the left-right (forward-backward) consistency check, the removal of small connected segments (as
+ * OpenCV's filterSpeckles does it) and a small median.  The matcher is symmetric, so the backward field costs no second
+ * match: the same records, read from their target's side (gpc_hip_flip_*), fill it.  The reference has no counterpart
+ * (it writes disparity.png from the raw supports); the rule is this library's own, made of integers only, so that every
+ * implementation of it gives the same bytes.
+ *
+ * Input: P = npairs fields fwd[P][C][height][width] int32 as gpc_hip_densify_* writes them, C = channels: 1 for a
+ *   disparity, 2 for u then v.  GPC_DENSE_NONE means no value; any other int32 is a value.  Optionally bwd[P][C][height]
+ *   [width], the field of the reversed records.  All sums and differences below are taken in 64 bits: no input value can
+ *   overflow them, and nothing is undefined for INT32_MAX or INT32_MIN + 1.  F_c(p) is fwd at pixel p in channel c, G_c bwd.
+ * Each pixel p = (x, y) has one STATE; the first rule that applies decides it:
+ *   1 none: F_0(p) is GPC_DENSE_NONE.
+ *   2 failed check (only with check_tol_q8 >= 0): r_c = sgn(F_c) * ((|F_c| + 128) >> 8) is the whole-pixel shift, rounded
+ *     half away from zero; the target is q = (x - r_0, y) with C = 1 and q = (x + r_0, y + r_1) with C = 2.  The pixel fails
+ *     when q is outside the image, or G_0(q) is GPC_DENSE_NONE, or |F_c(p) + G_c(q)| > check_tol_q8 in some channel.  (A
+ *     support's value is 256 d with the right pixel at x - d, and its reversed record has d' = -d: F + G is 0 for a
+ *     consistent pair, in both record types.)
+ *   3 speckle (only with speckle_min > 1): among the pixels that are not in state 1 or 2, two 4-neighbours p, q belong
+ *     together iff |F_c(p) - F_c(q)| <= speckle_diff_q8 in every channel; a pixel is a speckle iff its connected
+ *     component under the closure of this relation has fewer than speckle_min pixels.
+ *   0 kept: every other pixel.
+ * Outputs; every element of every output is written:
+ *   out[P][C][height][width]: a kept pixel gets, per channel, the lower median of F_c over the kept pixels of its
+ *     (2 r + 1)^2 window clipped to the image, r = median_radius: element (n - 1) >> 1 of the n values in ascending order;
+ *     with r = 0 that is F_c itself.  The medians read fwd, never out.  Every other pixel gets GPC_DENSE_NONE in every channel.
+ *   state[P][height][width] uint8 (optional).
+ *   label[P][height][width] int32 (optional): for a pixel not in state 1 or 2 the lowest pixel index y * width + x of its
+ *     component, otherwise -1.  Speckle pixels keep their label.  It is computed whenever it is asked for, whatever
+ *     speckle_min is.
+ *   stats[P][4] int32 (optional): the number of pixels in states 0, 1, 2 and 3.
+ * GPC_E_INVALID: a parameter out of range, channels not 1 or 2, check_tol_q8 >= 0 without bwd, a null required pointer, out
+ * overlapping fwd or bwd, width, height or npairs < 1.  GPC_E_UNSUPPORTED: width or height > 32768, width * height > 2^30,
+ * npairs > 65535 (the limits of the densify block). */
+typedef struct gpc_clean {
+  int32_t check_tol_q8;    /* -1 = no cross-check; 0 .. 2^24 otherwise, needs bwd                  */
+  int32_t speckle_diff_q8; /* 0 .. 2^24: neighbours belong together when they differ by at most it */
+  int32_t speckle_min;     /* 0 .. 2^30: a segment of fewer pixels is removed; 0 and 1 = none      */
+  int32_t median_radius;   /* 0 (none), 1 (3x3) or 2 (5x5)                                         */
+} gpc_clean;               /* documented defaults: 256, 256, 64, 1 */
+/* Fields already on the device.  A pure function of its arguments: no forest is needed, and the call only queues work on
+ * the context's stream (check; per-tile labelling, the union across tile edges, flatten and the size count where labels
+ * or sizes are needed; apply); read the outputs after gpc_hip_synchronize or another wait on the stream.  Workspaces of
+ * the context, grown on demand, per pixel and pair: 4 bytes for the labels (the fill's owner plane, which is free by then;
+ * d_label itself where it is given) and 4 for the sizes (only with speckle_min > 1). */
+int gpc_hip_clean_fields_device(gpc_hip_ctx* ctx, const int32_t* d_fwd, const int32_t* d_bwd, int channels, int width,
+                                int height, int npairs, const gpc_clean* prm, int32_t* d_out, uint8_t* d_state,
+                                int32_t* d_label, int32_t* d_stats);
+/* Reversed records, element-wise: slot i goes to slot i for i < m_t = min(max(d_counts[t], 0), cap_per_pair), so the counts
+ * stay valid; nothing else is written.  A correspondence (sx, sy, tx, ty) becomes (tx, ty, sx, sy).  A support (x, y, d)
+ * becomes (x - (int)d, y, -d) -- the subtraction wraps in 32 bits, -d flips the sign bit -- provided d is finite, whole and
+ * |d| < 2^24; otherwise it becomes (-1, -1, 0), which the fill ignores.  A refinement has dx_q8 and dy_q8 negated (in 16
+ * bits); cost and flags are copied.  d_ref and d_ref_out are optional, but go together (GPC_E_INVALID otherwise, as for a
+ * null required pointer, npairs or cap_per_pair < 1; GPC_E_UNSUPPORTED: npairs > 65535, npairs * cap_per_pair > 2^31 - 1).
+ * d_rec_out may be d_rec and d_ref_out d_ref (in place); any other overlap is undefined.  One launch on the context's stream. */
+int gpc_hip_flip_supports_device(gpc_hip_ctx* ctx, const gpc_support* d_rec, const gpc_refinement* d_ref, int cap_per_pair,
+                                 const int32_t* d_counts, int npairs, gpc_support* d_rec_out, gpc_refinement* d_ref_out);
+int gpc_hip_flip_correspondences_device(gpc_hip_ctx* ctx, const gpc_correspondence* d_rec, const gpc_refinement* d_ref,
+                                        int cap_per_pair, const int32_t* d_counts, int npairs, gpc_correspondence* d_rec_out,
+                                        gpc_refinement* d_ref_out);
+/* Match, refine, fill, flip, fill again, clean: exactly gpc_hip_densify_batch_device / gpc_hip_densify_sequence_device --
+ * the same settings, refinement, refusals, statuses, waiting and lane draining, group mode as there -- whose field is the
+ * forward field; then the records (and their refinements) are reversed where they lie, the reversed records are filled
+ * with the same gpc_densify into the backward field (only with check_tol_q8 >= 0), and gpc_hip_clean_fields_device runs
+ * over the two.  d_out is required; d_state, d_label, d_stats as above; d_fwd [P][C][height][width] (optional) receives the
+ * forward field and d_level (optional) its levels; d_counts and d_ncand (optional) as in the densify forms.  Workspaces of
+ * the context beyond those of the calls it is made of: the backward field, and the forward field where d_fwd is null. */
+int gpc_hip_clean_batch_device(gpc_hip_ctx* ctx, const uint8_t* d_rawL, const uint8_t* d_rawR, int width, int height, int npairs,
+                               const gpc_settings* settings, int refine_radius, const gpc_densify* fill, const gpc_clean* prm,
+                               int32_t* d_out, uint8_t* d_state, int32_t* d_label, int32_t* d_stats, int32_t* d_fwd,
+                               uint8_t* d_level, int32_t* d_counts, int32_t* d_ncand);
+int gpc_hip_clean_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int width, int height, int nframes,
+                                  const gpc_settings* settings, int refine_radius, const gpc_densify* fill, const gpc_clean* prm,
+                                  int32_t* d_out, uint8_t* d_state, int32_t* d_label, int32_t* d_stats, int32_t* d_fwd,
+                                  uint8_t* d_level, int32_t* d_counts, int32_t* d_ncand);
+/* Host fields and outputs through gpc_hip_clean_fields_device; synchronous, in chunks of at most 16 pairs, pageable arrays
+ * through the context's page-locked arena.  What comes back equals the device form byte for byte. */
+int gpc_hip_clean_fields(gpc_hip_ctx* ctx, const int32_t* fwd, const int32_t* bwd, int channels, int width, int height,
+                         int npairs, const gpc_clean* prm, int32_t* out, uint8_t* state, int32_t* label, int32_t* stats);
+
 /* ---- measurement -------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the context's stream.  When enabled every launch of
  * the named kernels is bracketed by hipEvents; gpc_hip_kernel_time returns the summed
@@ -1069,7 +1151,7 @@ int gpc_hip_enable_kernel_timing(gpc_hip_ctx* ctx, int enable);
 /* Restrict the bracketing to the kernels whose index bit is set (default: all).  Every pair of
  * event records costs a little stream time, so a benchmark times only the kernel it reports.  The mask has 32 bits and
  * gpc_hip_kernel_count() is the number of slots it addresses (at most 32).  gpc_hip_kernel_slots() counts every slot:
- * those from gpc_hip_kernel_count() on (k_refine, k_pyr_*, k_dense_*, k_tf_*, k_quad_*) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
+ * those from gpc_hip_kernel_count() on (k_refine, k_pyr_*, k_dense_*, k_tf_*, k_quad_*, k_clean_*) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
  * gpc_hip_kernel_launch_name and gpc_hip_kernel_time take their indices like any other. */
 int gpc_hip_set_kernel_timing_mask(gpc_hip_ctx* ctx, unsigned mask);
 int gpc_hip_reset_kernel_timing(gpc_hip_ctx* ctx);

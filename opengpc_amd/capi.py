@@ -82,6 +82,14 @@ class Densify(C.Structure):
         super().__init__(int(max_level), int(min_count), int(spread), int(max_cost))
 
 
+class Clean(C.Structure):
+    """gpc_clean: the parameters of the field cleaner (gpc_hip_clean_*); the documented defaults."""
+    _fields_ = [("check_tol_q8", C.c_int32), ("speckle_diff_q8", C.c_int32), ("speckle_min", C.c_int32), ("median_radius", C.c_int32)]
+
+    def __init__(self, check_tol_q8=256, speckle_diff_q8=256, speckle_min=64, median_radius=1):
+        super().__init__(int(check_tol_q8), int(speckle_diff_q8), int(speckle_min), int(median_radius))
+
+
 class FilterMask(C.Structure):
     """gpc::inference::Forest::FilterMask (reference inference.hpp:137-156)."""
     _fields_ = [
@@ -139,6 +147,8 @@ SYMBOLS = [
     "gpc_hip_densify_sequence_device", "gpc_hip_densify_supports", "gpc_hip_densify_correspondences",
     "gpc_hip_quads_records_device", "gpc_hip_match_stereo_sequence_device", "gpc_hip_quads_sequence_device",
     "gpc_hip_quads_records", "gpc_hip_quads_sequence",
+    "gpc_hip_clean_fields_device", "gpc_hip_flip_supports_device", "gpc_hip_flip_correspondences_device",
+    "gpc_hip_clean_batch_device", "gpc_hip_clean_sequence_device", "gpc_hip_clean_fields",
 ]
 
 
@@ -309,6 +319,15 @@ def load():
                                                 vp, ci, vp, vp, vp, vp, ci, vp]
     L.gpc_hip_quads_sequence.argtypes = L.gpc_hip_quads_sequence_device.argtypes
     L.gpc_hip_debug_live_resources.argtypes = [C.POINTER(C.c_uint64)]
+    L.gpc_hip_clean_fields_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Clean),
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_clean_fields.argtypes = L.gpc_hip_clean_fields_device.argtypes
+    L.gpc_hip_flip_supports_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.gpc_hip_flip_correspondences_device.argtypes = L.gpc_hip_flip_supports_device.argtypes
+    L.gpc_hip_clean_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
+                                             C.POINTER(Densify), C.POINTER(Clean)] + [C.c_void_p] * 8
+    L.gpc_hip_clean_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
+                                                C.POINTER(Densify), C.POINTER(Clean)] + [C.c_void_p] * 8
     _lib = L
     return L
 
@@ -1163,6 +1182,65 @@ class Context:
         fn = self.L.gpc_hip_densify_correspondences if corr else self.L.gpc_hip_densify_supports
         self._ck(fn(self.h, _ptr(records), cap, _ptr(counts), _ptr(ref), width, height, P, C.byref(prm), _ptr(value), _ptr(level)))
         return value, level
+
+    # ---- clean dense fields (gpc_hip_clean_*): cross-check, speckles, median
+    def clean_fields_device(self, d_fwd, channels, width, height, npairs, prm, d_out, d_bwd=0, d_state=0, d_label=0, d_stats=0):
+        """Fields [npairs][channels][height][width] int32 already in HBM, as the densify calls write them (d_bwd: the field of
+        the reversed records, needed when prm.check_tol_q8 >= 0) -> d_out of the same shape (DENSE_NONE where the pixel is not
+        kept), d_state [npairs][height][width] uint8, d_label [npairs][height][width] int32, d_stats [npairs][4] int32 (all
+        optional); asynchronous, no forest needed.  Pointers are integers."""
+        self._ck(self.L.gpc_hip_clean_fields_device(self.h, C.c_void_p(d_fwd), C.c_void_p(d_bwd or 0), int(channels), int(width),
+                                                    int(height), int(npairs), C.byref(prm), C.c_void_p(d_out), C.c_void_p(d_state or 0),
+                                                    C.c_void_p(d_label or 0), C.c_void_p(d_stats or 0)))
+
+    def flip_records_device(self, d_rec, corr, cap_per_pair, d_counts, npairs, d_rec_out, d_ref=0, d_ref_out=0):
+        """Records [npairs][cap_per_pair] in HBM (corr: CORR_DTYPE, else SUPPORT_DTYPE) read from their target's side, slot i to
+        slot i as far as the counts go; d_ref / d_ref_out: their refinements, shifts negated (both or neither).  In place is
+        allowed (d_rec_out == d_rec, d_ref_out == d_ref)."""
+        fn = self.L.gpc_hip_flip_correspondences_device if corr else self.L.gpc_hip_flip_supports_device
+        self._ck(fn(self.h, C.c_void_p(d_rec), C.c_void_p(d_ref or 0), int(cap_per_pair), C.c_void_p(d_counts), int(npairs),
+                    C.c_void_p(d_rec_out), C.c_void_p(d_ref_out or 0)))
+
+    def clean_batch_device(self, d_rawL, d_rawR, width, height, npairs, settings, fill, prm, d_out, d_state=0, d_label=0, d_stats=0,
+                           d_fwd=0, d_level=0, refine_radius=0, d_counts=0, d_ncand=0):
+        """densify_batch_device (its field is the forward field, d_fwd / d_level optional), the records reversed and filled
+        again, then clean_fields_device: d_out [npairs][1][height][width]."""
+        self._ck(self.L.gpc_hip_clean_batch_device(self.h, C.c_void_p(d_rawL), C.c_void_p(d_rawR), int(width), int(height), int(npairs),
+                                                   C.byref(settings), int(refine_radius), C.byref(fill), C.byref(prm),
+                                                   C.c_void_p(d_out), C.c_void_p(d_state or 0), C.c_void_p(d_label or 0),
+                                                   C.c_void_p(d_stats or 0), C.c_void_p(d_fwd or 0), C.c_void_p(d_level or 0),
+                                                   C.c_void_p(d_counts or 0), C.c_void_p(d_ncand or 0)))
+
+    def clean_sequence_device(self, d_frames, width, height, nframes, settings, fill, prm, d_out, d_state=0, d_label=0, d_stats=0,
+                              d_fwd=0, d_level=0, refine_radius=0, d_counts=0, d_ncand=0):
+        """densify_sequence_device, the records reversed and filled again, then clean_fields_device: d_out
+        [nframes-1][2][height][width]."""
+        self._ck(self.L.gpc_hip_clean_sequence_device(self.h, C.c_void_p(d_frames), int(width), int(height), int(nframes),
+                                                      C.byref(settings), int(refine_radius), C.byref(fill), C.byref(prm),
+                                                      C.c_void_p(d_out), C.c_void_p(d_state or 0), C.c_void_p(d_label or 0),
+                                                      C.c_void_p(d_stats or 0), C.c_void_p(d_fwd or 0), C.c_void_p(d_level or 0),
+                                                      C.c_void_p(d_counts or 0), C.c_void_p(d_ncand or 0)))
+
+    def clean_fields(self, fwd, bwd=None, prm=None, want_state=True, want_label=True, want_stats=True):
+        """Host fields [P, C, height, width] int32 (bwd optional: prm.check_tol_q8 must then be -1) -> (out [P, C, height,
+        width] int32, state [P, height, width] uint8, label [P, height, width] int32, stats [P, 4] int32; None where not
+        wanted)."""
+        fwd = np.ascontiguousarray(fwd, np.int32)
+        if fwd.ndim != 4 or fwd.shape[0] < 1:
+            raise ValueError("fwd: [P, C, height, width] int32")
+        if bwd is not None:
+            bwd = np.ascontiguousarray(bwd, np.int32)
+            if bwd.shape != fwd.shape:
+                raise ValueError("bwd: the shape of fwd")
+        prm = prm if prm is not None else Clean()
+        P, Cn, H, W = fwd.shape
+        out = np.empty(fwd.shape, np.int32)
+        state = np.empty((P, H, W), np.uint8) if want_state else None
+        label = np.empty((P, H, W), np.int32) if want_label else None
+        stats = np.empty((P, 4), np.int32) if want_stats else None
+        self._ck(self.L.gpc_hip_clean_fields(self.h, _ptr(fwd), _ptr(bwd), Cn, W, H, P, C.byref(prm), _ptr(out), _ptr(state),
+                                             _ptr(label), _ptr(stats)))
+        return out, state, label, stats
 
     # ---- stereo sequences (gpc_hip_quads_*): circular matches closed into quads on the device
     def quads_records_device(self, d_sup, cap_s, d_nsup, d_flowL, d_flowR, cap_f, d_nflowL, d_nflowR, width, height, nframes, tol,

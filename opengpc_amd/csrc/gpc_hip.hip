@@ -27,8 +27,10 @@
 #include <thread>
 #include <vector>
 
+#include "clean_host.h"
 #include "dense_host.h"
 #include "gpc_device.h"
+#include "k_clean.h"
 #include "k_consensus.h"
 #include "k_dense.h"
 #include "k_extract.h"
@@ -54,9 +56,9 @@
 #include "pyramid_host.h"
 #include "track_stream_host.h"
 
-// Six sections of the host code below are cut out at their rules into files of their own, csrc/host_*.h, and included where
+// Seven sections of the host code below are cut out at their rules into files of their own, csrc/host_*.h, and included where
 // they stood: host_staging.h (what scoring, tracks and the stages after them share), host_consensus.h, host_refine.h,
-// host_pyramid.h, host_dense.h and host_quads.h.  They are parts of THIS translation unit, not self-contained headers: each needs what
+// host_pyramid.h, host_dense.h, host_quads.h and host_clean.h.  They are parts of THIS translation unit, not self-contained headers: each needs what
 // stands above its include, and `#pragma once` is all the guard it has.  Each says its linkage once: an anonymous namespace
 // with its types, helpers and templates, then one extern "C" block with its entry points.  Everything else is still here.
 
@@ -115,6 +117,13 @@ enum KernelId {
   KID_QUAD_SETTLE,
   KID_QUAD_SCAN,
   KID_QUAD_WRITE,
+  KID_CLEAN_FLIP,
+  KID_CLEAN_CHECK,
+  KID_CLEAN_TILE,
+  KID_CLEAN_BORDER,
+  KID_CLEAN_FLATTEN,
+  KID_CLEAN_SIZES,
+  KID_CLEAN_APPLY,
   KID_COUNT
 };
 const char* const kKernelNames[KID_COUNT] = {
@@ -126,7 +135,8 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_score_records", "k_score_matchable", "k_refine", "k_pyr_down", "k_pyr_keep", "k_pyr_scan", "k_pyr_write",
     "k_dense_claim", "k_dense_pull", "k_dense_top", "k_dense_push",
     "k_tf_begin", "k_tf_eval", "k_tf_tot", "k_tf_commit",
-    "k_quad_sides", "k_quad_fill", "k_quad_scatter", "k_quad_close", "k_quad_settle", "k_quad_scan", "k_quad_write"};
+    "k_quad_sides", "k_quad_fill", "k_quad_scatter", "k_quad_close", "k_quad_settle", "k_quad_scan", "k_quad_write",
+    "k_clean_flip", "k_clean_check", "k_clean_tile", "k_clean_border", "k_clean_flatten", "k_clean_sizes", "k_clean_apply"};
 
 // The owners of owners.h over the HIP runtime.  Everything the library allocates passes through these four backends, which
 // also keep the process-wide counts that gpc_hip_debug_live_resources reports.
@@ -385,6 +395,9 @@ struct gpc_hip_ctx {
   // densifying (gpc_hip_densify_*): the owner plane, the counts and the sums of the cell pyramid, the refinements of the
   // match-and-fill forms
   DevBuf dn_owner, dn_n, dn_s, dn_ref;
+  // cleaning fields (gpc_hip_clean_*): the sizes of the components (the labels live in dn_owner or in the caller's plane); the
+  // forward field where the caller of a match-fill-and-clean form wants none, and the backward field
+  DevBuf cl_size, cl_fwd, cl_bwd;
   // quads over a stereo sequence (gpc_hip_quads_*): the per-pixel planes of a group of steps followed by its owner words
   // (one fill covers both), the candidate i' per support slot, the quad counts per chunk; the image-major copies of the
   // statistics words, code images and (32-bit codes) candidate bytes of each side, which the two flow joins of
@@ -4124,6 +4137,7 @@ int gpc_hip_track_stream_read_tracks(gpc_hip_ctx* c, gpc_hip_track_stream* s, in
 #include "host_pyramid.h"
 #include "host_dense.h"
 #include "host_quads.h"
+#include "host_clean.h"
 
 extern "C" {
 
