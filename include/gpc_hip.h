@@ -89,7 +89,8 @@ int gpc_hip_destroy(gpc_hip_ctx* ctx);
 /* Last HIP error text of this context (static storage inside the context). */
 const char* gpc_hip_last_error(const gpc_hip_ctx* ctx);
 /* Borrow an externally owned hipStream_t (e.g. torch's current stream); NULL restores
- * the context's own stream. */
+ * the context's own stream.  The caller waits for the old stream before switching: work still in flight on it shares the
+ * context's workspaces with whatever is queued on the new one, and nothing orders the two. */
 int gpc_hip_set_stream(gpc_hip_ctx* ctx, void* hip_stream);
 int gpc_hip_synchronize(gpc_hip_ctx* ctx);
 /* Pre-size device workspaces for `max_pairs` pairs of width x height (optional; the
