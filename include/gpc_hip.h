@@ -281,6 +281,10 @@ int gpc_hip_host_threads(const gpc_hip_ctx* ctx);
  * counts arrived), [2] the last chunk of packed records landed in host memory, [3] the expansion / delivery done (the
  * call returned).  All 0 for calls that took another path (one or two pairs written directly, the device-wide matchers). */
 int gpc_hip_batch_stages(const gpc_hip_ctx* ctx, float* ms4);
+/* The launch plan of the context's most recent k_hash launch: out = {tile height in rows (32 or 40), tiles a workgroup
+ * walks, workgroups per tile column (the grid's y), the flat workgroup index the launch's last round starts at}.  Host
+ * values recorded when the launch was queued: the call does not synchronise.  GPC_E_INVALID before the first launch. */
+int gpc_hip_hash_plan(gpc_hip_ctx* ctx, int32_t out[4]);
 /* The CPU each worker thread last ran a job on, or started on if it has run none yet (returns the number of workers;
  * fills at most cap entries). */
 int gpc_hip_host_worker_cpus(gpc_hip_ctx* ctx, int* cpus, int cap);

@@ -121,7 +121,7 @@ SYMBOLS = [
     "gpc_hip_rectified_match_begin", "gpc_hip_stereo_match_begin", "gpc_hip_match_pair_begin", "gpc_hip_match_fetch",
     "gpc_hip_hash_codes", "gpc_hip_rectified_match", "gpc_hip_stereo_match",
     "gpc_hip_match_pair", "gpc_hip_match_batch_device", "gpc_hip_set_pipeline", "gpc_hip_pipeline_join", "gpc_hip_match_batch",
-    "gpc_hip_match_batch_device_packed", "gpc_hip_match_batch_packed", "gpc_hip_expand_packed", "gpc_hip_host_threads", "gpc_hip_host_numa_node", "gpc_hip_batch_stages", "gpc_hip_host_worker_cpus", "gpc_hip_fed_calls",
+    "gpc_hip_match_batch_device_packed", "gpc_hip_match_batch_packed", "gpc_hip_expand_packed", "gpc_hip_host_threads", "gpc_hip_host_numa_node", "gpc_hip_batch_stages", "gpc_hip_hash_plan", "gpc_hip_host_worker_cpus", "gpc_hip_fed_calls",
     "gpc_hip_enable_kernel_timing", "gpc_hip_set_kernel_timing_mask", "gpc_hip_reset_kernel_timing", "gpc_hip_kernel_count", "gpc_hip_kernel_slots",
     "gpc_hip_kernel_name", "gpc_hip_kernel_launch_name", "gpc_hip_kernel_time",
     "gpc_hip_train_set_create", "gpc_hip_train_set_destroy", "gpc_hip_train_set_size", "gpc_hip_train_set_marks",
@@ -291,6 +291,7 @@ def load():
     L.gpc_hip_set_pipeline.argtypes = [C.c_void_p, C.c_int]
     L.gpc_hip_pipeline_join.argtypes = [C.c_void_p]
     L.gpc_hip_batch_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.gpc_hip_hash_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.gpc_hip_host_worker_cpus.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int]
     L.gpc_hip_enable_kernel_timing.argtypes = [C.c_void_p, C.c_int]
     L.gpc_hip_set_kernel_timing_mask.argtypes = [C.c_void_p, C.c_uint]
@@ -650,6 +651,13 @@ class Context:
         a = (C.c_float * 4)()
         self.L.gpc_hip_batch_stages(self.h, a)
         return [float(v) for v in a]
+
+    def hash_plan(self):
+        """(tile rows, tiles per workgroup, workgroups per tile column, first workgroup of the last round) of the context's
+        most recent k_hash launch (gpc_hip_hash_plan); raises GpcError (E_INVALID) before the first one."""
+        a = (C.c_int32 * 4)()
+        self._ck(self.L.gpc_hip_hash_plan(self.h, a))
+        return tuple(int(v) for v in a)
 
     def worker_cpus(self):
         a = (C.c_int * 64)()

@@ -442,6 +442,7 @@ struct gpc_hip_ctx {
   std::map<const void*, int> dyn_lds;     // largest dynamic-LDS size a kernel has been allowed so far (hipFuncSetAttribute once, not per call)
 
   int hash_tpw = 0;    // GPC_HIP_HASH_TPW: tiles per workgroup of the hash kernel (tuning)
+  int32_t hash_plan[4] = {0, 0, 0, 0};  // {ty, tpw, grid.y, last_from} of the last run_hash (gpc_hip_hash_plan); ty = 0: none yet
   int join_nt = 0;     // GPC_HIP_JOIN_NT = 256 | 512 | 1024: force the join kernel's threads per row (tuning)
 
   // rocprof name of the instantiation last launched under each timing slot (bench.py reports it)
@@ -972,6 +973,7 @@ int run_hash(gpc_hip_ctx* c, const uint8_t* d_smooth, const uint8_t* d_grad, con
   // the last `slots` workgroups in dispatch order: the launch's last round (k_hash.h: wave priority by the tiles left)
   const long nwg_all = (long)grid.x * grid.y * grid.z;
   const int last_from = nwg_all > slots ? (int)(nwg_all - slots) : 0;
+  c->hash_plan[0] = ty, c->hash_plan[1] = tpw, c->hash_plan[2] = (int32_t)grid.y, c->hash_plan[3] = last_from;
   Timed t(c, KID_HASH);
   const bool tau = groups > 0 ? c->gtau : c->forest.type != 0;
   int32_t* st = d_stats ? d_stats : (int32_t*)c->stats.p;  // (d_stats: as for run_preprocess)
@@ -4508,6 +4510,12 @@ int gpc_hip_host_threads(const gpc_hip_ctx* c) { return c ? c->pool.size() : 0; 
 int gpc_hip_batch_stages(const gpc_hip_ctx* c, float* ms4) {
   if (!c || !ms4) return GPC_E_INVALID;
   for (int i = 0; i < 4; ++i) ms4[i] = c->stage_ms[i];
+  return GPC_OK;
+}
+
+int gpc_hip_hash_plan(gpc_hip_ctx* c, int32_t out[4]) {
+  if (!c || !out || !c->hash_plan[0]) return GPC_E_INVALID;
+  for (int i = 0; i < 4; ++i) out[i] = c->hash_plan[i];
   return GPC_OK;
 }
 
