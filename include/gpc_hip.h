@@ -1148,6 +1148,74 @@ int gpc_hip_clean_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int
 int gpc_hip_clean_fields(gpc_hip_ctx* ctx, const int32_t* fwd, const int32_t* bwd, int channels, int width, int height,
                          int npairs, const gpc_clean* prm, int32_t* out, uint8_t* state, int32_t* label, int32_t* stats);
 
+/* ---- complete cleaned dense fields, guided by the image ------------------------------------ */
+/* The cleaner's output is a field with holes: failed checks (occlusions, halos), speckles, and whatever the fill never
+ * valued.  This stage closes them by an edge-aware completion: a hole takes the weighted mean of the valued pixels around
+ * it, and neighbours that look like it in the image count more, so that occluded background is filled from background.  The
+ * hierarchical fill cannot do it: it fills from records, not from a field, and averages across object edges.  The
+ * reference has no counterpart; the rule is this library's own, made of integers only, so that every implementation of it
+ * gives the same bytes.
+ *
+ * Input: P = npairs fields field[P][C][height][width] int32 as gpc_hip_densify_* and gpc_hip_clean_* write them, C =
+ *   channels: 1 or 2, and a guide guide[P][height][width] uint8: the raw left image, or frame t.  A pixel p is a HOLE iff
+ *   F_0(p) is GPC_DENSE_NONE, whatever F_1 holds; every other pixel is VALUED.  I(p) is the guide at p.
+ * Weight of neighbour q for pixel p: w(p, q) = 256 >> min(8, |I(p) - I(q)| >> range_shift): 1 .. 256, never 0; with
+ *   range_shift = 8 it is 256 always (unguided).
+ * Passes k = 1 .. passes.  State F(k) is a function of F(k-1) only (F(0) is the input): no value filled in pass k is read
+ *   in pass k.  For a hole p of F(k-1), Q is the set of valued pixels of F(k-1) in p's (2 radius + 1)^2 window clipped to
+ *   the image; Wt = sum over Q of w(p, q) and S_c = sum over Q of w(p, q) * F_c(q), both exact in 64 bits (no int32 input
+ *   can overflow them: |S| < 2^31 * 2^8 * 289 < 2^49).  If Wt >= min_weight, p becomes valued with sgn(S_c) * ((2 |S_c| +
+ *   Wt) div (2 Wt)) in channel c -- the fill's rounding, half away from zero -- and its pass number is k; otherwise it
+ *   stays a hole.  Valued pixels never change.
+ * Outputs; every element of every output is written:
+ *   out[P][C][height][width]: F(passes); a hole gets GPC_DENSE_NONE in every channel (also a hole of the input whose F_1
+ *     held something else).
+ *   pass[P][height][width] uint8 (optional): 0 for a pixel valued on input, k for a pixel filled in pass k, 255 for a pixel
+ *     left a hole.
+ *   stats[P][2] int32 (optional): pixels filled, holes left.
+ * out == field (the same pointer) is allowed and gives the same bytes; any other overlap of out with field is
+ * GPC_E_INVALID, as are a parameter out of range, channels not 1 or 2, a null required pointer (field, guide, out, prm),
+ * width, height or npairs < 1.  GPC_E_UNSUPPORTED: width or height > 32768, width * height > 2^30, npairs > 65535 (the
+ * limits of the densify block).  Once a pass fills nothing, or no hole is left, later passes change nothing: an
+ * implementation skips them, and tiles without holes, unobservably. */
+typedef struct gpc_inpaint {
+  int32_t radius;      /* 1 .. 8: the window is (2 r + 1)^2, clipped to the image              */
+  int32_t range_shift; /* 0 .. 8: the weight halves per 2^range_shift grey levels; 8 = unguided */
+  int32_t min_weight;  /* 1 .. 2^24: total weight a hole needs before it is filled              */
+  int32_t passes;      /* 1 .. 254                                                              */
+} gpc_inpaint;         /* documented defaults: 4, 3, 512, 32 -- a choice, not a measurement     */
+/* A field and a guide already on the device.  A pure function of its arguments: no forest is needed, and the call only
+ * queues work on the context's stream (two small clears, one launch that starts out and the pass plane, one launch per
+ * pass, in place in d_out; a pass with nothing left to do finds that out on the device -- the host reads no count and
+ * does not wait); read the outputs after gpc_hip_synchronize or another wait on the stream.  Workspaces of the context,
+ * grown on demand: 1 byte per pixel and pair for the pass plane (d_pass itself where it is given), and 4 bytes per 32x32
+ * tile and pair plus 1 KiB + 8 bytes per pair of control words. */
+int gpc_hip_inpaint_fields_device(gpc_hip_ctx* ctx, const int32_t* d_field, const uint8_t* d_guide, int channels, int width,
+                                  int height, int npairs, const gpc_inpaint* prm, int32_t* d_out, uint8_t* d_pass,
+                                  int32_t* d_stats);
+/* Match, refine, fill, flip, fill again, clean, complete: exactly gpc_hip_clean_batch_device / gpc_hip_clean_sequence_device
+ * -- the same settings, refusals, statuses, waiting, lane draining and group-mode behaviour -- then
+ * gpc_hip_inpaint_fields_device over the cleaned field, guided by d_rawL (batch) or by frame t for pair t (sequence).
+ * d_out (required) receives the completed field; d_pass and d_fill_stats (optional) are the pass plane and the stats of
+ * the completion; d_cleaned [P][C][height][width] (optional) receives the cleaned field before completion (it may not
+ * overlap d_out unless it is d_out, nor d_fwd); every other argument is the clean form's, d_state, d_label and d_stats
+ * describing the cleaned field.  Without d_cleaned the cleaner writes d_out and the completion runs in place: no
+ * workspace beyond those of the calls it is made of. */
+int gpc_hip_inpaint_batch_device(gpc_hip_ctx* ctx, const uint8_t* d_rawL, const uint8_t* d_rawR, int width, int height, int npairs,
+                                 const gpc_settings* settings, int refine_radius, const gpc_densify* fill, const gpc_clean* prm,
+                                 const gpc_inpaint* inpaint, int32_t* d_out, uint8_t* d_pass, int32_t* d_fill_stats,
+                                 int32_t* d_cleaned, uint8_t* d_state, int32_t* d_label, int32_t* d_stats, int32_t* d_fwd,
+                                 uint8_t* d_level, int32_t* d_counts, int32_t* d_ncand);
+int gpc_hip_inpaint_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int width, int height, int nframes,
+                                    const gpc_settings* settings, int refine_radius, const gpc_densify* fill, const gpc_clean* prm,
+                                    const gpc_inpaint* inpaint, int32_t* d_out, uint8_t* d_pass, int32_t* d_fill_stats,
+                                    int32_t* d_cleaned, uint8_t* d_state, int32_t* d_label, int32_t* d_stats, int32_t* d_fwd,
+                                    uint8_t* d_level, int32_t* d_counts, int32_t* d_ncand);
+/* A host field, guide and outputs through gpc_hip_inpaint_fields_device; synchronous, in chunks of at most 16 pairs, pageable
+ * arrays through the context's page-locked arena.  What comes back equals the device form byte for byte. */
+int gpc_hip_inpaint_fields(gpc_hip_ctx* ctx, const int32_t* field, const uint8_t* guide, int channels, int width, int height,
+                           int npairs, const gpc_inpaint* prm, int32_t* out, uint8_t* pass, int32_t* stats);
+
 /* ---- measurement -------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the context's stream.  When enabled every launch of
  * the named kernels is bracketed by hipEvents; gpc_hip_kernel_time returns the summed
@@ -1156,7 +1224,7 @@ int gpc_hip_enable_kernel_timing(gpc_hip_ctx* ctx, int enable);
 /* Restrict the bracketing to the kernels whose index bit is set (default: all).  Every pair of
  * event records costs a little stream time, so a benchmark times only the kernel it reports.  The mask has 32 bits and
  * gpc_hip_kernel_count() is the number of slots it addresses (at most 32).  gpc_hip_kernel_slots() counts every slot:
- * those from gpc_hip_kernel_count() on (k_refine, k_pyr_*, k_dense_*, k_tf_*, k_quad_*, k_clean_*) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
+ * those from gpc_hip_kernel_count() on (k_refine, k_pyr_*, k_dense_*, k_tf_*, k_inpaint_*, k_quad_*, k_clean_*) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
  * gpc_hip_kernel_launch_name and gpc_hip_kernel_time take their indices like any other. */
 int gpc_hip_set_kernel_timing_mask(gpc_hip_ctx* ctx, unsigned mask);
 int gpc_hip_reset_kernel_timing(gpc_hip_ctx* ctx);

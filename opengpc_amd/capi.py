@@ -90,6 +90,14 @@ class Clean(C.Structure):
         super().__init__(int(check_tol_q8), int(speckle_diff_q8), int(speckle_min), int(median_radius))
 
 
+class Inpaint(C.Structure):
+    """gpc_inpaint: the parameters of the guided completion (gpc_hip_inpaint_*); the documented defaults."""
+    _fields_ = [("radius", C.c_int32), ("range_shift", C.c_int32), ("min_weight", C.c_int32), ("passes", C.c_int32)]
+
+    def __init__(self, radius=4, range_shift=3, min_weight=512, passes=32):
+        super().__init__(int(radius), int(range_shift), int(min_weight), int(passes))
+
+
 class FilterMask(C.Structure):
     """gpc::inference::Forest::FilterMask (reference inference.hpp:137-156)."""
     _fields_ = [
@@ -149,6 +157,7 @@ SYMBOLS = [
     "gpc_hip_quads_records", "gpc_hip_quads_sequence",
     "gpc_hip_clean_fields_device", "gpc_hip_flip_supports_device", "gpc_hip_flip_correspondences_device",
     "gpc_hip_clean_batch_device", "gpc_hip_clean_sequence_device", "gpc_hip_clean_fields",
+    "gpc_hip_inpaint_fields_device", "gpc_hip_inpaint_batch_device", "gpc_hip_inpaint_sequence_device", "gpc_hip_inpaint_fields",
 ]
 
 
@@ -329,6 +338,13 @@ def load():
                                              C.POINTER(Densify), C.POINTER(Clean)] + [C.c_void_p] * 8
     L.gpc_hip_clean_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
                                                 C.POINTER(Densify), C.POINTER(Clean)] + [C.c_void_p] * 8
+    L.gpc_hip_inpaint_fields_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Inpaint),
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_inpaint_fields.argtypes = L.gpc_hip_inpaint_fields_device.argtypes
+    L.gpc_hip_inpaint_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
+                                               C.POINTER(Densify), C.POINTER(Clean), C.POINTER(Inpaint)] + [C.c_void_p] * 11
+    L.gpc_hip_inpaint_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
+                                                  C.POINTER(Densify), C.POINTER(Clean), C.POINTER(Inpaint)] + [C.c_void_p] * 11
     _lib = L
     return L
 
@@ -1249,6 +1265,56 @@ class Context:
         self._ck(self.L.gpc_hip_clean_fields(self.h, _ptr(fwd), _ptr(bwd), Cn, W, H, P, C.byref(prm), _ptr(out), _ptr(state),
                                              _ptr(label), _ptr(stats)))
         return out, state, label, stats
+
+    # ---- complete cleaned fields (gpc_hip_inpaint_*): holes take the guided weighted mean of the valued pixels around them
+    def inpaint_fields_device(self, d_field, d_guide, channels, width, height, npairs, prm, d_out, d_pass=0, d_stats=0):
+        """A field [npairs][channels][height][width] int32 and a guide [npairs][height][width] uint8 already in HBM -> d_out of
+        the field's shape (it may be d_field itself), d_pass [npairs][height][width] uint8, d_stats [npairs][2] int32 (both
+        optional); asynchronous, no forest needed.  Pointers are integers."""
+        self._ck(self.L.gpc_hip_inpaint_fields_device(self.h, C.c_void_p(d_field), C.c_void_p(d_guide), int(channels), int(width),
+                                                      int(height), int(npairs), C.byref(prm), C.c_void_p(d_out), C.c_void_p(d_pass or 0),
+                                                      C.c_void_p(d_stats or 0)))
+
+    def inpaint_batch_device(self, d_rawL, d_rawR, width, height, npairs, settings, fill, prm, inpaint, d_out, d_pass=0, d_fill_stats=0,
+                             d_cleaned=0, d_state=0, d_label=0, d_stats=0, d_fwd=0, d_level=0, refine_radius=0, d_counts=0, d_ncand=0):
+        """clean_batch_device (its field goes to d_cleaned, optional), then inpaint_fields_device guided by the left images:
+        d_out [npairs][1][height][width]."""
+        self._ck(self.L.gpc_hip_inpaint_batch_device(self.h, C.c_void_p(d_rawL), C.c_void_p(d_rawR), int(width), int(height), int(npairs),
+                                                     C.byref(settings), int(refine_radius), C.byref(fill), C.byref(prm), C.byref(inpaint),
+                                                     C.c_void_p(d_out), C.c_void_p(d_pass or 0), C.c_void_p(d_fill_stats or 0),
+                                                     C.c_void_p(d_cleaned or 0), C.c_void_p(d_state or 0), C.c_void_p(d_label or 0),
+                                                     C.c_void_p(d_stats or 0), C.c_void_p(d_fwd or 0), C.c_void_p(d_level or 0),
+                                                     C.c_void_p(d_counts or 0), C.c_void_p(d_ncand or 0)))
+
+    def inpaint_sequence_device(self, d_frames, width, height, nframes, settings, fill, prm, inpaint, d_out, d_pass=0, d_fill_stats=0,
+                                d_cleaned=0, d_state=0, d_label=0, d_stats=0, d_fwd=0, d_level=0, refine_radius=0, d_counts=0,
+                                d_ncand=0):
+        """clean_sequence_device, then inpaint_fields_device guided by frame t: d_out [nframes-1][2][height][width]."""
+        self._ck(self.L.gpc_hip_inpaint_sequence_device(self.h, C.c_void_p(d_frames), int(width), int(height), int(nframes),
+                                                        C.byref(settings), int(refine_radius), C.byref(fill), C.byref(prm),
+                                                        C.byref(inpaint), C.c_void_p(d_out), C.c_void_p(d_pass or 0),
+                                                        C.c_void_p(d_fill_stats or 0), C.c_void_p(d_cleaned or 0),
+                                                        C.c_void_p(d_state or 0), C.c_void_p(d_label or 0), C.c_void_p(d_stats or 0),
+                                                        C.c_void_p(d_fwd or 0), C.c_void_p(d_level or 0), C.c_void_p(d_counts or 0),
+                                                        C.c_void_p(d_ncand or 0)))
+
+    def inpaint_fields(self, field, guide, prm=None, want_pass=True, want_stats=True):
+        """A host field [P, C, height, width] int32 and guide [P, height, width] uint8 -> (out [P, C, height, width] int32, pass
+        [P, height, width] uint8, stats [P, 2] int32; None where not wanted)."""
+        field = np.ascontiguousarray(field, np.int32)
+        guide = np.ascontiguousarray(guide, np.uint8)
+        if field.ndim != 4 or field.shape[0] < 1:
+            raise ValueError("field: [P, C, height, width] int32")
+        P, Cn, H, W = field.shape
+        if guide.shape != (P, H, W):
+            raise ValueError("guide: [P, height, width] uint8")
+        prm = prm if prm is not None else Inpaint()
+        out = np.empty(field.shape, np.int32)
+        pas = np.empty((P, H, W), np.uint8) if want_pass else None
+        stats = np.empty((P, 2), np.int32) if want_stats else None
+        self._ck(self.L.gpc_hip_inpaint_fields(self.h, _ptr(field), _ptr(guide), Cn, W, H, P, C.byref(prm), _ptr(out), _ptr(pas),
+                                               _ptr(stats)))
+        return out, pas, stats
 
     # ---- stereo sequences (gpc_hip_quads_*): circular matches closed into quads on the device
     def quads_records_device(self, d_sup, cap_s, d_nsup, d_flowL, d_flowR, cap_f, d_nflowL, d_nflowR, width, height, nframes, tol,

@@ -30,6 +30,7 @@
 #include "clean_host.h"
 #include "dense_host.h"
 #include "gpc_device.h"
+#include "inpaint_host.h"
 #include "k_clean.h"
 #include "k_consensus.h"
 #include "k_dense.h"
@@ -38,6 +39,7 @@
 #include "k_hash.h"
 #include "k_hashtable.h"
 #include "k_htjoin.h"
+#include "k_inpaint.h"
 #include "k_partition.h"
 #include "k_preprocess.h"
 #include "k_pyramid.h"
@@ -56,9 +58,9 @@
 #include "pyramid_host.h"
 #include "track_stream_host.h"
 
-// Seven sections of the host code below are cut out at their rules into files of their own, csrc/host_*.h, and included where
+// Eight sections of the host code below are cut out at their rules into files of their own, csrc/host_*.h, and included where
 // they stood: host_staging.h (what scoring, tracks and the stages after them share), host_consensus.h, host_refine.h,
-// host_pyramid.h, host_dense.h, host_quads.h and host_clean.h.  They are parts of THIS translation unit, not self-contained headers: each needs what
+// host_pyramid.h, host_dense.h, host_quads.h, host_clean.h and host_inpaint.h.  They are parts of THIS translation unit, not self-contained headers: each needs what
 // stands above its include, and `#pragma once` is all the guard it has.  Each says its linkage once: an anonymous namespace
 // with its types, helpers and templates, then one extern "C" block with its entry points.  Everything else is still here.
 
@@ -110,6 +112,8 @@ enum KernelId {
   KID_TF_EVAL,
   KID_TF_TOT,
   KID_TF_COMMIT,
+  KID_INPAINT_BEGIN,
+  KID_INPAINT_PASS,
   KID_QUAD_SIDES,
   KID_QUAD_FILL,
   KID_QUAD_SCATTER,
@@ -135,6 +139,7 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_score_records", "k_score_matchable", "k_refine", "k_pyr_down", "k_pyr_keep", "k_pyr_scan", "k_pyr_write",
     "k_dense_claim", "k_dense_pull", "k_dense_top", "k_dense_push",
     "k_tf_begin", "k_tf_eval", "k_tf_tot", "k_tf_commit",
+    "k_inpaint_begin", "k_inpaint_pass",
     "k_quad_sides", "k_quad_fill", "k_quad_scatter", "k_quad_close", "k_quad_settle", "k_quad_scan", "k_quad_write",
     "k_clean_flip", "k_clean_check", "k_clean_tile", "k_clean_border", "k_clean_flatten", "k_clean_sizes", "k_clean_apply"};
 
@@ -398,6 +403,9 @@ struct gpc_hip_ctx {
   // cleaning fields (gpc_hip_clean_*): the sizes of the components (the labels live in dn_owner or in the caller's plane); the
   // forward field where the caller of a match-fill-and-clean form wants none, and the backward field
   DevBuf cl_size, cl_fwd, cl_bwd;
+  // completing fields (gpc_hip_inpaint_*): the pass plane where the caller passes none; the control words (pixels filled per
+  // pass, stats where the caller passes none, holes per tile)
+  DevBuf ip_pass, ip_ctl;
   // quads over a stereo sequence (gpc_hip_quads_*): the per-pixel planes of a group of steps followed by its owner words
   // (one fill covers both), the candidate i' per support slot, the quad counts per chunk; the image-major copies of the
   // statistics words, code images and (32-bit codes) candidate bytes of each side, which the two flow joins of
@@ -4140,6 +4148,7 @@ int gpc_hip_track_stream_read_tracks(gpc_hip_ctx* c, gpc_hip_track_stream* s, in
 #include "host_dense.h"
 #include "host_quads.h"
 #include "host_clean.h"
+#include "host_inpaint.h"
 
 extern "C" {
 
