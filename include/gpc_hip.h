@@ -1148,6 +1148,81 @@ int gpc_hip_clean_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int
 int gpc_hip_clean_fields(gpc_hip_ctx* ctx, const int32_t* fwd, const int32_t* bwd, int channels, int width, int height,
                          int npairs, const gpc_clean* prm, int32_t* out, uint8_t* state, int32_t* label, int32_t* stats);
 
+/* ---- search the image pair around every pixel of a dense field ------------------------------ */
+/* The fill of gpc_hip_densify_* gives a pixel the mean of the matches in a block around it: an interpolation, right to a
+ * pixel or two on smooth surfaces and wrong across object edges, and no later stage compares the two images at a pixel that
+ * had no match of its own.  This stage does, as ELAS does with its supports: the filled value is a prior, and a small search
+ * around it in the other image, by the SAD cost and the parabola of gpc_hip_refine_*, replaces it with what the images say.
+ * It belongs between the fill and the cleaner.  The reference has no counterpart; the rule is this library's own, made of
+ * integers only, so that every implementation of it gives the same bytes.
+ *
+ * Input: P = npairs fields field[P][C][height][width] int32 in 1/256 pixel as gpc_hip_densify_* writes them, C = channels: 1
+ *   for a disparity, 2 for u then v; imgL[P][height][width] and imgR[P][height][width] uint8.  A pixel p is a HOLE iff F_0(p)
+ *   is GPC_DENSE_NONE, whatever F_1 holds; every other pixel is VALUED.  All arithmetic on field values is done in 64 bits:
+ *   nothing is undefined for INT32_MAX, INT32_MIN + 1 or an F_1 that is GPC_DENSE_NONE.  r = radius, R = range.
+ * Per valued pixel p = (x, y):
+ *   1 pixels by clamped address: I(img, x, y) = img[clamp(y, 0, height-1)][clamp(x, 0, width-1)], and
+ *     cost(p, t) = sum over |i|, |j| <= r of |I(imgL, x+i, y+j) - I(imgR, tx+i, ty+j)|: border pixels are evaluated like any
+ *     other.  The largest cost is 81 * 255 = 20655.
+ *   2 base target: r_c = sgn(F_c) * ((|F_c| + 128) >> 8), the cleaner's rounding; b = (x - r_0, y) with C = 1 and
+ *     b = (x + r_0, y + r_1) with C = 2.
+ *   3 candidates: k = (kx, 0), |kx| <= R with C = 1; k = (kx, ky), |kx|, |ky| <= R with C = 2.  Candidate k has the target
+ *     t_k = b + k and is ADMISSIBLE iff t_k lies inside the image.  A valued pixel without an admissible candidate is UNMATCHED.
+ *   4 best: the admissible candidate with the lexicographically smallest (cost, |kx| + |ky|, ky, kx): on equal cost the
+ *     prior wins, then the nearer candidate, then a fixed order.
+ *   5 sub-pixel shift (only with subpixel = 1), per axis -- x always, y only with C = 2: when both neighbours of t_best
+ *     along the axis lie inside the image (they need not be candidates), their costs c-, c+ and c0 = cost(p, t_best) go
+ *     through the parabola of gpc_hip_refine_*: a = c- + c+ - 2 c0, n = c- - c+; the axis has a minimum iff c0 <= c-,
+ *     c0 <= c+ and a > 0, and then q = sgn(n) * ((256 |n| + a) div 2a); otherwise q = 0.
+ *   6 value: 256 (r_0 - kx) - qx with C = 1; u = 256 (r_0 + kx) + qx and v = 256 (r_1 + ky) + qy with C = 2: the
+ *     conventions of the fill.  Admissibility bounds |r_c| by the image size, so nothing overflows.
+ *   7 a matched pixel with c0 > max_cost is REJECTED.
+ * Outputs; every element of every output is written:
+ *   out[P][C][height][width]: the value for a matched pixel that is not rejected (KEPT); GPC_DENSE_NONE in every channel for
+ *     holes, unmatched and rejected pixels.  out == field (the same pointer) is allowed and gives the same bytes: a pixel
+ *     reads only its own field value.
+ *   cost[P][height][width] uint16 (optional): c0 of the best candidate, also for a rejected pixel; 0xFFFF for holes and
+ *     unmatched pixels.
+ *   choice[P][height][width] uint8 (optional): (ky + R) (2R + 1) + (kx + R) of the best candidate, kx + R with C = 1; 255
+ *     for holes and unmatched pixels.
+ *   stats[P][4] int32 (optional): the numbers of pixels kept, hole, unmatched and rejected.
+ * GPC_E_INVALID: a parameter out of range, channels not 1 or 2, a null required pointer (field, imgL, imgR, out, prm), width,
+ * height or npairs < 1, out overlapping field other than being it, out overlapping an image.  GPC_E_UNSUPPORTED: width or
+ * height > 32768, width * height > 2^30, npairs > 65535 (the limits of the densify block).  r <= 4 and R <= 2 keep a target
+ * row with all its shifts within 2r + 1 + 2(R + 1) <= 15 bytes, one 16-byte load. */
+typedef struct gpc_search {
+  int32_t radius;    /* r, 1 .. 4: the window is (2 r + 1)^2                                   */
+  int32_t range;     /* R, 0 .. 2: candidates within R whole pixels of the base; 0 = verify only */
+  int32_t subpixel;  /* 0 or 1                                                                  */
+  int32_t max_cost;  /* 0 .. 0xFFFF; 0xFFFF = no ceiling                                        */
+} gpc_search;        /* documented defaults: 2, 1, 1, 0xFFFF -- a choice, not a measurement     */
+/* A field and its two images already on the device.  A pure function of its arguments: no forest is needed, and the call
+ * only queues work on the context's stream (a clear of the stats, one launch); read the outputs after gpc_hip_synchronize or
+ * another wait on the stream.  No workspace. */
+int gpc_hip_search_fields_device(gpc_hip_ctx* ctx, const int32_t* d_field, const uint8_t* d_imgL, const uint8_t* d_imgR,
+                                 int channels, int width, int height, int npairs, const gpc_search* prm, int32_t* d_out,
+                                 uint16_t* d_cost, uint8_t* d_choice, int32_t* d_stats);
+/* Match, refine, fill, search, flip, fill again, search with the two images exchanged, clean: exactly
+ * gpc_hip_clean_batch_device / gpc_hip_clean_sequence_device -- the same settings, refusals, statuses, waiting, lane draining
+ * and group-mode behaviour -- with gpc_hip_search_fields_device run in place over the forward field and (only with
+ * check_tol_q8 >= 0) over the backward field.  The images are d_rawL and d_rawR (batch), frames t and t + 1 for pair t
+ * (sequence).  d_fwd (optional) receives the searched forward field and d_cost [P][height][width] (optional) its costs; every
+ * other argument is the clean form's.  No workspace beyond those of the calls it is made of.  Completion
+ * (gpc_hip_inpaint_fields_device) over the result is composed by the caller. */
+int gpc_hip_search_batch_device(gpc_hip_ctx* ctx, const uint8_t* d_rawL, const uint8_t* d_rawR, int width, int height, int npairs,
+                                const gpc_settings* settings, int refine_radius, const gpc_densify* fill, const gpc_search* search,
+                                const gpc_clean* prm, int32_t* d_out, uint8_t* d_state, int32_t* d_label, int32_t* d_stats,
+                                int32_t* d_fwd, uint8_t* d_level, int32_t* d_counts, int32_t* d_ncand, uint16_t* d_cost);
+int gpc_hip_search_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int width, int height, int nframes,
+                                   const gpc_settings* settings, int refine_radius, const gpc_densify* fill, const gpc_search* search,
+                                   const gpc_clean* prm, int32_t* d_out, uint8_t* d_state, int32_t* d_label, int32_t* d_stats,
+                                   int32_t* d_fwd, uint8_t* d_level, int32_t* d_counts, int32_t* d_ncand, uint16_t* d_cost);
+/* A host field, images and outputs through gpc_hip_search_fields_device; synchronous, in chunks of at most 16 pairs, pageable
+ * arrays through the context's page-locked arena.  What comes back equals the device form byte for byte. */
+int gpc_hip_search_fields(gpc_hip_ctx* ctx, const int32_t* field, const uint8_t* imgL, const uint8_t* imgR, int channels, int width,
+                          int height, int npairs, const gpc_search* prm, int32_t* out, uint16_t* cost, uint8_t* choice,
+                          int32_t* stats);
+
 /* ---- complete cleaned dense fields, guided by the image ------------------------------------ */
 /* The cleaner's output is a field with holes: failed checks (occlusions, halos), speckles, and whatever the fill never
  * valued.  This stage closes them by an edge-aware completion: a hole takes the weighted mean of the valued pixels around
@@ -1224,7 +1299,7 @@ int gpc_hip_enable_kernel_timing(gpc_hip_ctx* ctx, int enable);
 /* Restrict the bracketing to the kernels whose index bit is set (default: all).  Every pair of
  * event records costs a little stream time, so a benchmark times only the kernel it reports.  The mask has 32 bits and
  * gpc_hip_kernel_count() is the number of slots it addresses (at most 32).  gpc_hip_kernel_slots() counts every slot:
- * those from gpc_hip_kernel_count() on (k_refine, k_pyr_*, k_dense_*, k_tf_*, k_inpaint_*, k_quad_*, k_clean_*) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
+ * those from gpc_hip_kernel_count() on (k_search, k_refine, k_pyr_*, k_dense_*, k_tf_*, k_inpaint_*, k_quad_*, k_clean_*) are bracketed whenever timing is enabled, and gpc_hip_kernel_name,
  * gpc_hip_kernel_launch_name and gpc_hip_kernel_time take their indices like any other. */
 int gpc_hip_set_kernel_timing_mask(gpc_hip_ctx* ctx, unsigned mask);
 int gpc_hip_reset_kernel_timing(gpc_hip_ctx* ctx);

@@ -90,6 +90,14 @@ class Clean(C.Structure):
         super().__init__(int(check_tol_q8), int(speckle_diff_q8), int(speckle_min), int(median_radius))
 
 
+class Search(C.Structure):
+    """gpc_search: the parameters of the local dense search (gpc_hip_search_*); the documented defaults."""
+    _fields_ = [("radius", C.c_int32), ("range", C.c_int32), ("subpixel", C.c_int32), ("max_cost", C.c_int32)]
+
+    def __init__(self, radius=2, range=1, subpixel=1, max_cost=0xFFFF):
+        super().__init__(int(radius), int(range), int(subpixel), int(max_cost))
+
+
 class Inpaint(C.Structure):
     """gpc_inpaint: the parameters of the guided completion (gpc_hip_inpaint_*); the documented defaults."""
     _fields_ = [("radius", C.c_int32), ("range_shift", C.c_int32), ("min_weight", C.c_int32), ("passes", C.c_int32)]
@@ -158,6 +166,7 @@ SYMBOLS = [
     "gpc_hip_clean_fields_device", "gpc_hip_flip_supports_device", "gpc_hip_flip_correspondences_device",
     "gpc_hip_clean_batch_device", "gpc_hip_clean_sequence_device", "gpc_hip_clean_fields",
     "gpc_hip_inpaint_fields_device", "gpc_hip_inpaint_batch_device", "gpc_hip_inpaint_sequence_device", "gpc_hip_inpaint_fields",
+    "gpc_hip_search_fields_device", "gpc_hip_search_batch_device", "gpc_hip_search_sequence_device", "gpc_hip_search_fields",
 ]
 
 
@@ -345,6 +354,13 @@ def load():
                                                C.POINTER(Densify), C.POINTER(Clean), C.POINTER(Inpaint)] + [C.c_void_p] * 11
     L.gpc_hip_inpaint_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
                                                   C.POINTER(Densify), C.POINTER(Clean), C.POINTER(Inpaint)] + [C.c_void_p] * 11
+    L.gpc_hip_search_fields_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.POINTER(Search), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_search_fields.argtypes = L.gpc_hip_search_fields_device.argtypes
+    L.gpc_hip_search_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
+                                              C.POINTER(Densify), C.POINTER(Search), C.POINTER(Clean)] + [C.c_void_p] * 9
+    L.gpc_hip_search_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
+                                                 C.POINTER(Densify), C.POINTER(Search), C.POINTER(Clean)] + [C.c_void_p] * 9
     _lib = L
     return L
 
@@ -1265,6 +1281,54 @@ class Context:
         self._ck(self.L.gpc_hip_clean_fields(self.h, _ptr(fwd), _ptr(bwd), Cn, W, H, P, C.byref(prm), _ptr(out), _ptr(state),
                                              _ptr(label), _ptr(stats)))
         return out, state, label, stats
+
+    # ---- search the image pair around every pixel of a field (gpc_hip_search_*): the filled value is the prior
+    def search_fields_device(self, d_field, d_imgL, d_imgR, channels, width, height, npairs, prm, d_out, d_cost=0, d_choice=0, d_stats=0):
+        """A field [npairs][channels][height][width] int32 and the images [npairs][height][width] uint8 already in HBM -> d_out
+        of the field's shape (it may be d_field itself), d_cost [npairs][height][width] uint16, d_choice [npairs][height][width]
+        uint8, d_stats [npairs][4] int32 (all optional); asynchronous, no forest needed.  Pointers are integers."""
+        self._ck(self.L.gpc_hip_search_fields_device(self.h, C.c_void_p(d_field), C.c_void_p(d_imgL), C.c_void_p(d_imgR), int(channels),
+                                                     int(width), int(height), int(npairs), C.byref(prm), C.c_void_p(d_out),
+                                                     C.c_void_p(d_cost or 0), C.c_void_p(d_choice or 0), C.c_void_p(d_stats or 0)))
+
+    def search_batch_device(self, d_rawL, d_rawR, width, height, npairs, settings, fill, search, prm, d_out, d_state=0, d_label=0,
+                            d_stats=0, d_fwd=0, d_level=0, refine_radius=0, d_counts=0, d_ncand=0, d_cost=0):
+        """clean_batch_device with search_fields_device run in place over the forward field (d_fwd, its costs d_cost) and, with
+        the images exchanged, over the backward field: d_out [npairs][1][height][width]."""
+        self._ck(self.L.gpc_hip_search_batch_device(self.h, C.c_void_p(d_rawL), C.c_void_p(d_rawR), int(width), int(height), int(npairs),
+                                                    C.byref(settings), int(refine_radius), C.byref(fill), C.byref(search), C.byref(prm),
+                                                    C.c_void_p(d_out), C.c_void_p(d_state or 0), C.c_void_p(d_label or 0),
+                                                    C.c_void_p(d_stats or 0), C.c_void_p(d_fwd or 0), C.c_void_p(d_level or 0),
+                                                    C.c_void_p(d_counts or 0), C.c_void_p(d_ncand or 0), C.c_void_p(d_cost or 0)))
+
+    def search_sequence_device(self, d_frames, width, height, nframes, settings, fill, search, prm, d_out, d_state=0, d_label=0,
+                               d_stats=0, d_fwd=0, d_level=0, refine_radius=0, d_counts=0, d_ncand=0, d_cost=0):
+        """clean_sequence_device with the search over frames t and t + 1 behind each fill: d_out [nframes-1][2][height][width]."""
+        self._ck(self.L.gpc_hip_search_sequence_device(self.h, C.c_void_p(d_frames), int(width), int(height), int(nframes),
+                                                       C.byref(settings), int(refine_radius), C.byref(fill), C.byref(search),
+                                                       C.byref(prm), C.c_void_p(d_out), C.c_void_p(d_state or 0),
+                                                       C.c_void_p(d_label or 0), C.c_void_p(d_stats or 0), C.c_void_p(d_fwd or 0),
+                                                       C.c_void_p(d_level or 0), C.c_void_p(d_counts or 0), C.c_void_p(d_ncand or 0),
+                                                       C.c_void_p(d_cost or 0)))
+
+    def search_fields(self, field, imgL, imgR, prm=None, want_cost=True, want_choice=True, want_stats=True):
+        """A host field [P, C, height, width] int32 and images [P, height, width] uint8 -> (out [P, C, height, width] int32, cost
+        [P, height, width] uint16, choice [P, height, width] uint8, stats [P, 4] int32; None where not wanted)."""
+        field = np.ascontiguousarray(field, np.int32)
+        imgL, imgR = np.ascontiguousarray(imgL, np.uint8), np.ascontiguousarray(imgR, np.uint8)
+        if field.ndim != 4 or field.shape[0] < 1:
+            raise ValueError("field: [P, C, height, width] int32")
+        P, Cn, H, W = field.shape
+        if imgL.shape != (P, H, W) or imgR.shape != (P, H, W):
+            raise ValueError("imgL, imgR: [P, height, width] uint8")
+        prm = prm if prm is not None else Search()
+        out = np.empty(field.shape, np.int32)
+        cost = np.empty((P, H, W), np.uint16) if want_cost else None
+        choice = np.empty((P, H, W), np.uint8) if want_choice else None
+        stats = np.empty((P, 4), np.int32) if want_stats else None
+        self._ck(self.L.gpc_hip_search_fields(self.h, _ptr(field), _ptr(imgL), _ptr(imgR), Cn, W, H, P, C.byref(prm), _ptr(out),
+                                              _ptr(cost), _ptr(choice), _ptr(stats)))
+        return out, cost, choice, stats
 
     # ---- complete cleaned fields (gpc_hip_inpaint_*): holes take the guided weighted mean of the valued pixels around them
     def inpaint_fields_device(self, d_field, d_guide, channels, width, height, npairs, prm, d_out, d_pass=0, d_stats=0):

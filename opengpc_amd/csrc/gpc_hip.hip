@@ -49,6 +49,7 @@
 #include "k_rowjoin_fused.h"
 #include "k_rows.h"
 #include "k_score.h"
+#include "k_search.h"
 #include "k_track.h"
 #include "k_track_stream.h"
 #include "k_train.h"
@@ -56,6 +57,7 @@
 #include "k_union.h"
 #include "owners.h"
 #include "pyramid_host.h"
+#include "search_host.h"
 #include "track_stream_host.h"
 
 // Eight sections of the host code below are cut out at their rules into files of their own, csrc/host_*.h, and included where
@@ -99,6 +101,7 @@ enum KernelId {
   KID_TRS_NCAND,
   KID_SCORE_RECORDS,
   KID_SCORE_MATCHABLE,
+  KID_SEARCH,
   KID_REFINE,
   KID_PYR_DOWN,
   KID_PYR_KEEP,
@@ -136,7 +139,7 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_track_fill", "k_track_scatter", "k_track_link", "k_track_settle", "k_track_scan", "k_track_walk",
     "k_cons_cells", "k_cons_scan", "k_cons_scatter", "k_cons_count", "k_cons_blocks", "k_cons_write",
     "k_trs_fill", "k_trs_scatter", "k_trs_link", "k_trs_settle", "k_trs_scan", "k_trs_walk", "k_trs_save", "k_trs_ncand",
-    "k_score_records", "k_score_matchable", "k_refine", "k_pyr_down", "k_pyr_keep", "k_pyr_scan", "k_pyr_write",
+    "k_score_records", "k_score_matchable", "k_search", "k_refine", "k_pyr_down", "k_pyr_keep", "k_pyr_scan", "k_pyr_write",
     "k_dense_claim", "k_dense_pull", "k_dense_top", "k_dense_push",
     "k_tf_begin", "k_tf_eval", "k_tf_tot", "k_tf_commit",
     "k_inpaint_begin", "k_inpaint_pass",
@@ -4148,6 +4151,7 @@ int gpc_hip_track_stream_read_tracks(gpc_hip_ctx* c, gpc_hip_track_stream* s, in
 #include "host_dense.h"
 #include "host_quads.h"
 #include "host_clean.h"
+#include "host_search.h"
 #include "host_inpaint.h"
 
 extern "C" {
