@@ -1291,6 +1291,83 @@ int gpc_hip_inpaint_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, i
 int gpc_hip_inpaint_fields(gpc_hip_ctx* ctx, const int32_t* field, const uint8_t* guide, int channels, int width, int height,
                            int npairs, const gpc_inpaint* prm, int32_t* out, uint8_t* pass, int32_t* stats);
 
+/* ---- score dense fields against ground truth ------------------------------------------------ */
+/* How good a field is, as exact counts per pair: end-point error, the share of pixels within a few pixels of truth, the
+ * KITTI outlier rate (D1 for a disparity, Fl for a flow), the density, and all of it split by an occlusion class or by the
+ * speed of the true motion, as Sintel and KITTI report it.  gpc_hip_score_* above judges sparse records and cannot take a
+ * field; this block judges what gpc_hip_densify_*, gpc_hip_search_*, gpc_hip_clean_* and gpc_hip_inpaint_* write, where it
+ * lies.  The rule uses integers only, so that every implementation of it gives the same bytes.  The library returns counts
+ * only; rates are the caller's divisions.
+ *
+ * Input: P = npairs fields field[P][C][height][width] int32 in 1/256 pixel as gpc_hip_densify_* writes them, C = channels: 1
+ *   for a disparity, 2 for u then v; a gpc_truth (above): u[P][height][width] float, v likewise (it must be NULL with C = 1
+ *   and is required with C = 2), ignore[P][height][width] uint8 (optional); cls[P][height][width] uint8 (optional).
+ * A pixel is, in this order:
+ *   1 IGNORED: ignore is given and nonzero at the pixel.
+ *   2 NO TRUTH: a truth value that is read (u; also v with C = 2) is not finite or its absolute value exceeds 32768 (the
+ *     image-size limit; the .flo "unknown" sentinel 1e9 lies beyond it).
+ *   3 HOLE: F_0 is GPC_DENSE_NONE, whatever F_1 holds (the rule of the search block).
+ *   4 JUDGED: every other pixel.
+ * Error of a judged pixel, all arithmetic in 64 bits:
+ *   t_c = llrintf(256.f * truth_c): the product is exact, the rounding to nearest, ties to even (KITTI's truth is in 1/256
+ *     pixel exactly); |t_c| <= 2^23.
+ *   d_c = (int64)F_c - t_c, with C = 1 as with C = 2: a disparity field holds 256 d and the truth g is a disparity.
+ *   a_c = min(|d_c|, 65536); a_1 = 0 with C = 1.
+ *   e2 = min(a_0^2 + a_1^2, 2^32); e = isqrt(e2), the exact floor of the square root.
+ *   Errors beyond 256 pixels are clamped; a clamped pixel lies within no threshold because thr_q8 <= 65535.  Nothing is
+ *   undefined for INT32_MAX, INT32_MIN + 1 or an F_1 that is GPC_DENSE_NONE.
+ * Tallies over judged pixels (gpc_field_tally): n_judged; n_within[k] counts e2 <= thr_q8[k]^2 (entries at k >= n_thr are
+ *   0); sum_e_q8 sums e; sum_e2_q16 sums e2; n_outlier counts e2 > out_abs_q8^2 and e2 * 10^6 > m2 * out_rel_pm^2 with m2 =
+ *   t_0^2 + t_1^2 (both sides fit uint64: out_rel_pm is per mille and at most 255).  KITTI's rule is out_abs_q8 = 768,
+ *   out_rel_pm = 50; out_rel_pm = 0 is the absolute test alone.
+ * Bin of a judged pixel: with cls, min(cls, 3); otherwise the number of k < n_speed with m2 >= speed_q8[k]^2 (speed_q8
+ *   ascending; Sintel's s0-10 / s10-40 / s40+ is {2560, 10240}); with neither, bin 0.
+ * Identities: n_pixels = width * height = n_ignored + n_no_truth + n_hole + all.n_judged, and `all` equals the elementwise
+ *   sum of the four bins.
+ * err[P][height][width] uint16 (optional): min(e, 0xFFFE) for a judged pixel, 0xFFFF for every other; every element is
+ *   written.
+ * GPC_E_INVALID: a parameter out of range (of thr_q8 and speed_q8 the entries in use are looked at), reserved not 0, a null
+ * required pointer (field, truth, truth->u, prm, scores), channels not 1 or 2, truth->v given with C = 1 or missing with
+ * C = 2, width, height or npairs < 1.  GPC_E_UNSUPPORTED: width or height > 32768, width * height > 2^30, npairs > 65535
+ * (the limits of the densify block).  No alignment is required beyond each type's own, unlike gpc_hip_score_batch_device. */
+typedef struct gpc_field_score_prm {
+  int32_t n_thr;        /* 0 .. 8: thresholds in use                                                     */
+  int32_t thr_q8[8];    /* 0 .. 65535 each, in 1/256 pixel                                               */
+  int32_t out_abs_q8;   /* 0 .. 65535: an outlier's error exceeds this ...                               */
+  int32_t out_rel_pm;   /* 0 .. 255: ... and this many per mille of the true magnitude; 0 = absolute only */
+  int32_t n_speed;      /* 0 .. 3: speed bounds in use (only without cls)                                */
+  int32_t speed_q8[3];  /* 0 .. 2^23 each, ascending, in 1/256 pixel                                     */
+  int32_t reserved;     /* must be 0                                                                     */
+} gpc_field_score_prm;  /* documented defaults: n_thr 3, thr_q8 {256, 768, 1280}, out 768 / 50, n_speed 0 */
+typedef struct gpc_field_tally {  /* every field an exact count or sum over judged pixels */
+  int64_t n_judged;
+  int64_t n_within[8];
+  int64_t n_outlier;
+  int64_t sum_e_q8;
+  int64_t sum_e2_q16;
+} gpc_field_tally;                /* 96 bytes */
+typedef struct gpc_field_score {  /* one per pair */
+  int64_t n_pixels;
+  int64_t n_ignored;
+  int64_t n_no_truth;
+  int64_t n_hole;
+  gpc_field_tally all;
+  gpc_field_tally bin[4];
+} gpc_field_score;                /* 512 bytes */
+/* Fields, truth and class plane already on the device (truth holds device pointers).  A pure function of its arguments: no
+ * forest and no workspace are needed, and the call only queues work on the context's stream (a clear of d_scores, one
+ * launch); read d_scores[npairs] and d_err after gpc_hip_synchronize or another wait on the stream.  The kernel has no
+ * timing slot (the slot table is closed): time it with events on the stream. */
+int gpc_hip_score_fields_device(gpc_hip_ctx* ctx, const int32_t* d_field, int channels, int width, int height, int npairs,
+                                const gpc_truth* truth, const gpc_field_score_prm* prm, const uint8_t* d_cls,
+                                gpc_field_score* d_scores, uint16_t* d_err);
+/* Host fields, truth (host pointers), class plane, scores and error plane through gpc_hip_score_fields_device; synchronous,
+ * in chunks of at most 16 pairs, pageable arrays through the context's page-locked arena.  What comes back equals the device
+ * form byte for byte. */
+int gpc_hip_score_fields(gpc_hip_ctx* ctx, const int32_t* field, int channels, int width, int height, int npairs,
+                         const gpc_truth* truth, const gpc_field_score_prm* prm, const uint8_t* cls, gpc_field_score* scores,
+                         uint16_t* err);
+
 /* ---- measurement -------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the context's stream.  When enabled every launch of
  * the named kernels is bracketed by hipEvents; gpc_hip_kernel_time returns the summed

@@ -63,6 +63,62 @@ class Truth(C.Structure):
     _fields_ = [("u", C.c_void_p), ("v", C.c_void_p), ("ignore", C.c_void_p)]
 
 
+class FieldScorePrm(C.Structure):
+    """gpc_field_score_prm: the parameters of the dense field scorer (gpc_hip_score_fields*); the documented defaults."""
+    _fields_ = [("n_thr", C.c_int32), ("thr_q8", C.c_int32 * 8), ("out_abs_q8", C.c_int32), ("out_rel_pm", C.c_int32),
+                ("n_speed", C.c_int32), ("speed_q8", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+    def __init__(self, thr_q8=(256, 768, 1280), out_abs_q8=768, out_rel_pm=50, speed_q8=(), n_thr=None, n_speed=None, reserved=0):
+        thr_q8, speed_q8 = [int(t) for t in thr_q8], [int(t) for t in speed_q8]
+        if len(thr_q8) > 8 or len(speed_q8) > 3:
+            raise ValueError("at most 8 thresholds and 3 speed bounds")
+        super().__init__(len(thr_q8) if n_thr is None else int(n_thr), (C.c_int32 * 8)(*thr_q8), int(out_abs_q8), int(out_rel_pm),
+                         len(speed_q8) if n_speed is None else int(n_speed), (C.c_int32 * 3)(*speed_q8), int(reserved))
+
+
+class FieldTally(C.Structure):
+    """gpc_field_tally: exact counts and sums over judged pixels."""
+    _fields_ = [("n_judged", C.c_int64), ("n_within", C.c_int64 * 8), ("n_outlier", C.c_int64), ("sum_e_q8", C.c_int64),
+                ("sum_e2_q16", C.c_int64)]
+
+
+class FieldScore(C.Structure):
+    """gpc_field_score: one pair's counts.  The library returns counts only; the accessors divide them on the host, over all
+    judged pixels or (bin = 0 .. 3) over one bin's, and return nan where nothing was judged."""
+    _fields_ = [("n_pixels", C.c_int64), ("n_ignored", C.c_int64), ("n_no_truth", C.c_int64), ("n_hole", C.c_int64),
+                ("all", FieldTally), ("bin", FieldTally * 4)]
+
+    def tally(self, bin=None):
+        return self.all if bin is None else self.bin[int(bin)]
+
+    @staticmethod
+    def _div(a, b):
+        return float(a) / float(b) if b else float("nan")
+
+    def epe(self, bin=None):
+        """the mean end-point error in pixels"""
+        t = self.tally(bin)
+        return self._div(t.sum_e_q8, 256 * t.n_judged)
+
+    def rms(self, bin=None):
+        """the root of the mean squared error in pixels"""
+        t = self.tally(bin)
+        return self._div(t.sum_e2_q16, 65536 * t.n_judged) ** 0.5
+
+    def within(self, k, bin=None):
+        """the share of judged pixels within threshold k"""
+        t = self.tally(bin)
+        return self._div(t.n_within[int(k)], t.n_judged)
+
+    def outlier_rate(self, bin=None):
+        t = self.tally(bin)
+        return self._div(t.n_outlier, t.n_judged)
+
+    def density(self, bin=None):
+        """judged pixels over the pixels that could be judged (judged + holes); a bin's share of them with bin given"""
+        return self._div(self.tally(bin).n_judged, self.all.n_judged + self.n_hole)
+
+
 class Consensus(C.Structure):
     """gpc_consensus: the parameters of the grid motion consensus filter (gpc_hip_consensus_*); the documented defaults."""
     _fields_ = [("cell", C.c_int32), ("shifts", C.c_int32), ("alpha_num", C.c_int32), ("alpha_den", C.c_int32)]
@@ -167,6 +223,7 @@ SYMBOLS = [
     "gpc_hip_clean_batch_device", "gpc_hip_clean_sequence_device", "gpc_hip_clean_fields",
     "gpc_hip_inpaint_fields_device", "gpc_hip_inpaint_batch_device", "gpc_hip_inpaint_sequence_device", "gpc_hip_inpaint_fields",
     "gpc_hip_search_fields_device", "gpc_hip_search_batch_device", "gpc_hip_search_sequence_device", "gpc_hip_search_fields",
+    "gpc_hip_score_fields_device", "gpc_hip_score_fields",
 ]
 
 
@@ -361,6 +418,9 @@ def load():
                                               C.POINTER(Densify), C.POINTER(Search), C.POINTER(Clean)] + [C.c_void_p] * 9
     L.gpc_hip_search_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
                                                  C.POINTER(Densify), C.POINTER(Search), C.POINTER(Clean)] + [C.c_void_p] * 9
+    L.gpc_hip_score_fields_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Truth),
+                                              C.POINTER(FieldScorePrm), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_score_fields.argtypes = L.gpc_hip_score_fields_device.argtypes
     _lib = L
     return L
 
@@ -918,6 +978,36 @@ class Context:
         self._ck(self.L.gpc_hip_score_sequence(self.h, _ptr(frames), W, H, N, C.byref(settings), C.byref(tr), _ptr(t), len(t),
                                                _ptr(scores)))
         return scores
+
+    # ---- dense fields against ground truth (gpc_hip_score_fields*): exact counts per pair, the field scored where it lies
+    def score_fields_device(self, d_field, channels, width, height, npairs, d_u, d_v, d_ignore, prm, d_scores, d_cls=0, d_err=0):
+        """A field [npairs][channels][height][width] int32 and truth planes [npairs][height][width] (d_u, d_v float32; d_v 0 for
+        a disparity; d_ignore and d_cls uint8, optional) already in HBM -> d_scores [npairs] of FieldScore (512 bytes each),
+        d_err [npairs][height][width] uint16 (optional); asynchronous, no forest needed.  Pointers are integers."""
+        tr = Truth(d_u or None, d_v or None, d_ignore or None)
+        self._ck(self.L.gpc_hip_score_fields_device(self.h, C.c_void_p(d_field), int(channels), int(width), int(height), int(npairs),
+                                                    C.byref(tr), C.byref(prm), C.c_void_p(d_cls or 0), C.c_void_p(d_scores),
+                                                    C.c_void_p(d_err or 0)))
+
+    def score_fields(self, field, u, v=None, ignore=None, prm=None, cls=None, want_err=False):
+        """A host field [P, C, height, width] int32 against host truth planes [P, height, width] (u, v float32; v None for a
+        disparity; ignore, cls uint8 or None) -> (a ctypes array of P FieldScore, err [P, height, width] uint16 or None)."""
+        field = np.ascontiguousarray(field, np.int32)
+        if field.ndim != 4 or field.shape[0] < 1:
+            raise ValueError("field: [P, C, height, width] int32")
+        P, Cn, H, W = field.shape
+        plane = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt)
+        u, v, ignore, cls = plane(u, np.float32), plane(v, np.float32), plane(ignore, np.uint8), plane(cls, np.uint8)
+        for a in (u, v, ignore, cls):
+            if a is not None and a.shape != (P, H, W):
+                raise ValueError("truth, ignore, cls: [P, height, width]")
+        prm = prm if prm is not None else FieldScorePrm()
+        scores = (FieldScore * P)()
+        err = np.empty((P, H, W), np.uint16) if want_err else None
+        tr = Truth(*[a.ctypes.data if a is not None else None for a in (u, v, ignore)])
+        self._ck(self.L.gpc_hip_score_fields(self.h, _ptr(field), Cn, W, H, P, C.byref(tr), C.byref(prm), _ptr(cls),
+                                             C.cast(scores, C.c_void_p), _ptr(err)))
+        return scores, err
 
     # ---- point tracks (gpc_hip_track_*): the records of consecutive pairs chained on the device
     def track_records_device(self, d_corr, cap_per_pair, d_counts, width, height, npairs, d_next, d_track_id, d_tracks,

@@ -29,12 +29,14 @@
 
 #include "clean_host.h"
 #include "dense_host.h"
+#include "field_score_host.h"
 #include "gpc_device.h"
 #include "inpaint_host.h"
 #include "k_clean.h"
 #include "k_consensus.h"
 #include "k_dense.h"
 #include "k_extract.h"
+#include "k_field_score.h"
 #include "k_global.h"
 #include "k_hash.h"
 #include "k_hashtable.h"
@@ -62,7 +64,7 @@
 
 // Eight sections of the host code below are cut out at their rules into files of their own, csrc/host_*.h, and included where
 // they stood: host_staging.h (what scoring, tracks and the stages after them share), host_consensus.h, host_refine.h,
-// host_pyramid.h, host_dense.h, host_quads.h, host_clean.h and host_inpaint.h.  They are parts of THIS translation unit, not self-contained headers: each needs what
+// host_pyramid.h, host_dense.h, host_quads.h, host_clean.h, host_inpaint.h and host_field_score.h (host_search.h came between).  They are parts of THIS translation unit, not self-contained headers: each needs what
 // stands above its include, and `#pragma once` is all the guard it has.  Each says its linkage once: an anonymous namespace
 // with its types, helpers and templates, then one extern "C" block with its entry points.  Everything else is still here.
 
@@ -4153,6 +4155,7 @@ int gpc_hip_track_stream_read_tracks(gpc_hip_ctx* c, gpc_hip_track_stream* s, in
 #include "host_clean.h"
 #include "host_search.h"
 #include "host_inpaint.h"
+#include "host_field_score.h"
 
 extern "C" {
 
