@@ -1223,6 +1223,75 @@ int gpc_hip_search_fields(gpc_hip_ctx* ctx, const int32_t* field, const uint8_t*
                           int height, int npairs, const gpc_search* prm, int32_t* out, uint16_t* cost, uint8_t* choice,
                           int32_t* stats);
 
+/* ---- aggregate the search's costs along scanlines ------------------------------------------- */
+/* The search above lets every pixel decide alone: a tie or a near-tie in a weakly textured window is settled by a fixed
+ * order, and nothing asks whether the pixel beside it chose the same displacement.  This stage is a second way to choose
+ * among the SAME candidates by the SAME costs: before the choice a smoothness term is added along scanlines, in the form of
+ * the path aggregation of semi-global matching, which stays in integers.  It sits where the search sits, between the fill
+ * and the cleaner.  The search itself is unchanged.
+ *
+ * Inputs, I, cost(p, t), the base r_c and b, the candidates k, their targets t_k and admissibility are those of steps 1 - 3
+ * of the search block.  p1 <= p2 are the penalties; the bits of `paths` name where the predecessor q of p = (x, y) lies:
+ *   1: q = (x-1, y), the path runs left to right      2: q = (x+1, y), right to left
+ *   4: q = (x, y-1), top to bottom                     8: q = (x, y+1), bottom to top
+ * A pixel is LIVE iff it is valued and has at least one admissible candidate; A(p) is the set of its admissible candidates
+ * and c(p, k) = cost(p, t_k).  The displacement of a candidate is d(p, k) = t_k - p: (kx - r_0(p), 0) with C = 1,
+ * (r_0(p) + kx, r_1(p) + ky) with C = 2.  The penalty of a difference v of two displacements is V(v) = 0 for v = 0, p1 for
+ * max(|v_x|, |v_y|) = 1, p2 otherwise.  For a live p, k in A(p) and a direction with predecessor q:
+ *   q inside the image and live:  L(p, k) = c(p, k) + min over j in A(q) of [L(q, j) + V(d(p, k) - d(q, j))]
+ *                                                   - min over j in A(q) of L(q, j)
+ *   otherwise (the border, a hole, an unmatched pixel alike) the path starts anew:  L(p, k) = c(p, k).
+ * The bracket less the minimum lies in [0, p2], so 0 <= L <= 20655 + 32767 < 2^16 and a sum over four paths fits 18 bits.
+ * (d(p, k) - d(q, j) depends only on k - j and on the difference of the two bases, so an implementation need look only at
+ * the label of equal displacement, its up to 8 (C = 2) or 2 (C = 1) neighbours and the overall minimum, not at all pairs;
+ * the plain minimum above is the definition.)
+ * S(p, k) is the sum of L over the directions in `paths`; with paths = 0, S(p, k) = c(p, k).
+ *   4' best: the admissible candidate with the lexicographically smallest (S, |kx| + |ky|, ky, kx).
+ * Steps 5 - 7 of the search block follow unchanged, on the RAW costs around t_best: the parabola, the value, the ceiling, so
+ * max_cost and the cost output mean what they mean there.  With paths = 0 (any p1, p2) or p1 = p2 = 0 (any paths) S is a
+ * positive multiple of c, and out, cost, choice and stats equal those of gpc_hip_search_fields byte for byte.
+ * Outputs; every element of every output is written:
+ *   out, cost (c0 of the best, raw), choice, stats[P][4]: exactly as the search block defines them.
+ *   agg[P][height][width] uint32 (optional): S of the best candidate, also for a rejected pixel; 0xFFFFFFFF for holes and
+ *     unmatched pixels.
+ * The refusals of the search block apply; p1, p2 or paths out of range give GPC_E_INVALID.  out == field is allowed and
+ * gives the same bytes. */
+typedef struct gpc_aggregate {
+  int32_t radius, range, subpixel, max_cost;  /* as gpc_search, same ranges                                          */
+  int32_t p1, p2;                             /* 0 <= p1 <= p2 <= 32767                                              */
+  int32_t paths;                              /* 0 .. 15, the bits above                                             */
+} gpc_aggregate;     /* documented defaults: 2, 1, 1, 0xFFFF as gpc_search; p1 = 128, p2 = 512, paths = 15: chosen on
+                      * four synthetic scenes (the lowest error over all pixels of a small grid, by a margin of 0.1 %:
+                      * DESIGN.md 4.20)                                                                              */
+/* A field and its two images already on the device.  A pure function of its arguments: no forest is needed, and the call
+ * only queues work on the context's stream (a clear of the stats; per group of pairs one launch for the cost volume, one
+ * per orientation of the paths and one for the choice); read the outputs after gpc_hip_synchronize or another wait on the
+ * stream.  Workspace, owned by the context and grown on demand: per pixel 2 bytes for each of the (2R+3) (C = 1) or
+ * (2R+3)^2 (C = 2) cells of the cost volume and 2 bytes per label and direction for the path values -- 10 + 6 d (C = 1),
+ * 50 + 18 d (C = 2) bytes at R = 1 with d directions.  Pairs go through the launches in groups sized to stay within 1 GiB,
+ * at least one pair a group; the result does not depend on the grouping. */
+int gpc_hip_aggregate_fields_device(gpc_hip_ctx* ctx, const int32_t* d_field, const uint8_t* d_imgL, const uint8_t* d_imgR,
+                                    int channels, int width, int height, int npairs, const gpc_aggregate* prm, int32_t* d_out,
+                                    uint16_t* d_cost, uint8_t* d_choice, int32_t* d_stats, uint32_t* d_agg);
+/* gpc_hip_search_batch_device / gpc_hip_search_sequence_device with this stage in the search's place, over the forward
+ * field and, only with check_tol_q8 >= 0, over the backward field with the images exchanged: the same settings, refusals,
+ * statuses, waiting, lane draining and group-mode behaviour; d_cost as there. */
+int gpc_hip_aggregate_batch_device(gpc_hip_ctx* ctx, const uint8_t* d_rawL, const uint8_t* d_rawR, int width, int height,
+                                   int npairs, const gpc_settings* settings, int refine_radius, const gpc_densify* fill,
+                                   const gpc_aggregate* aggregate, const gpc_clean* prm, int32_t* d_out, uint8_t* d_state,
+                                   int32_t* d_label, int32_t* d_stats, int32_t* d_fwd, uint8_t* d_level, int32_t* d_counts,
+                                   int32_t* d_ncand, uint16_t* d_cost);
+int gpc_hip_aggregate_sequence_device(gpc_hip_ctx* ctx, const uint8_t* d_frames, int width, int height, int nframes,
+                                      const gpc_settings* settings, int refine_radius, const gpc_densify* fill,
+                                      const gpc_aggregate* aggregate, const gpc_clean* prm, int32_t* d_out, uint8_t* d_state,
+                                      int32_t* d_label, int32_t* d_stats, int32_t* d_fwd, uint8_t* d_level, int32_t* d_counts,
+                                      int32_t* d_ncand, uint16_t* d_cost);
+/* A host field, images and outputs through gpc_hip_aggregate_fields_device; synchronous, in chunks of at most 16 pairs,
+ * pageable arrays through the context's page-locked arena.  What comes back equals the device form byte for byte. */
+int gpc_hip_aggregate_fields(gpc_hip_ctx* ctx, const int32_t* field, const uint8_t* imgL, const uint8_t* imgR, int channels,
+                             int width, int height, int npairs, const gpc_aggregate* prm, int32_t* out, uint16_t* cost,
+                             uint8_t* choice, int32_t* stats, uint32_t* agg);
+
 /* ---- complete cleaned dense fields, guided by the image ------------------------------------ */
 /* The cleaner's output is a field with holes: failed checks (occlusions, halos), speckles, and whatever the fill never
  * valued.  This stage closes them by an edge-aware completion: a hole takes the weighted mean of the valued pixels around

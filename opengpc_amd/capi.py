@@ -154,6 +154,16 @@ class Search(C.Structure):
         super().__init__(int(radius), int(range), int(subpixel), int(max_cost))
 
 
+class Aggregate(C.Structure):
+    """gpc_aggregate: the parameters of the scanline aggregation of the search's costs (gpc_hip_aggregate_*); the documented
+    defaults.  The bits of paths: 1 left to right, 2 right to left, 4 top to bottom, 8 bottom to top."""
+    _fields_ = [("radius", C.c_int32), ("range", C.c_int32), ("subpixel", C.c_int32), ("max_cost", C.c_int32), ("p1", C.c_int32),
+                ("p2", C.c_int32), ("paths", C.c_int32)]
+
+    def __init__(self, radius=2, range=1, subpixel=1, max_cost=0xFFFF, p1=128, p2=512, paths=15):
+        super().__init__(int(radius), int(range), int(subpixel), int(max_cost), int(p1), int(p2), int(paths))
+
+
 class Inpaint(C.Structure):
     """gpc_inpaint: the parameters of the guided completion (gpc_hip_inpaint_*); the documented defaults."""
     _fields_ = [("radius", C.c_int32), ("range_shift", C.c_int32), ("min_weight", C.c_int32), ("passes", C.c_int32)]
@@ -224,6 +234,8 @@ SYMBOLS = [
     "gpc_hip_inpaint_fields_device", "gpc_hip_inpaint_batch_device", "gpc_hip_inpaint_sequence_device", "gpc_hip_inpaint_fields",
     "gpc_hip_search_fields_device", "gpc_hip_search_batch_device", "gpc_hip_search_sequence_device", "gpc_hip_search_fields",
     "gpc_hip_score_fields_device", "gpc_hip_score_fields",
+    "gpc_hip_aggregate_fields_device", "gpc_hip_aggregate_batch_device", "gpc_hip_aggregate_sequence_device",
+    "gpc_hip_aggregate_fields",
 ]
 
 
@@ -418,6 +430,13 @@ def load():
                                               C.POINTER(Densify), C.POINTER(Search), C.POINTER(Clean)] + [C.c_void_p] * 9
     L.gpc_hip_search_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
                                                  C.POINTER(Densify), C.POINTER(Search), C.POINTER(Clean)] + [C.c_void_p] * 9
+    L.gpc_hip_aggregate_fields_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(Aggregate), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_aggregate_fields.argtypes = L.gpc_hip_aggregate_fields_device.argtypes
+    L.gpc_hip_aggregate_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
+                                                 C.POINTER(Densify), C.POINTER(Aggregate), C.POINTER(Clean)] + [C.c_void_p] * 9
+    L.gpc_hip_aggregate_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
+                                                    C.POINTER(Densify), C.POINTER(Aggregate), C.POINTER(Clean)] + [C.c_void_p] * 9
     L.gpc_hip_score_fields_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Truth),
                                               C.POINTER(FieldScorePrm), C.c_void_p, C.c_void_p, C.c_void_p]
     L.gpc_hip_score_fields.argtypes = L.gpc_hip_score_fields_device.argtypes
@@ -1419,6 +1438,57 @@ class Context:
         self._ck(self.L.gpc_hip_search_fields(self.h, _ptr(field), _ptr(imgL), _ptr(imgR), Cn, W, H, P, C.byref(prm), _ptr(out),
                                               _ptr(cost), _ptr(choice), _ptr(stats)))
         return out, cost, choice, stats
+
+    # ---- aggregate the search's costs along scanlines (gpc_hip_aggregate_*): the search's candidates, chosen with a smoothness term
+    def aggregate_fields_device(self, d_field, d_imgL, d_imgR, channels, width, height, npairs, prm, d_out, d_cost=0, d_choice=0,
+                                d_stats=0, d_agg=0):
+        """search_fields_device with the choice made over the aggregated costs; d_agg [npairs][height][width] uint32 (optional)
+        receives the best candidate's sum.  Asynchronous, no forest needed.  Pointers are integers."""
+        self._ck(self.L.gpc_hip_aggregate_fields_device(self.h, C.c_void_p(d_field), C.c_void_p(d_imgL), C.c_void_p(d_imgR), int(channels),
+                                                        int(width), int(height), int(npairs), C.byref(prm), C.c_void_p(d_out),
+                                                        C.c_void_p(d_cost or 0), C.c_void_p(d_choice or 0), C.c_void_p(d_stats or 0),
+                                                        C.c_void_p(d_agg or 0)))
+
+    def aggregate_batch_device(self, d_rawL, d_rawR, width, height, npairs, settings, fill, aggregate, prm, d_out, d_state=0, d_label=0,
+                               d_stats=0, d_fwd=0, d_level=0, refine_radius=0, d_counts=0, d_ncand=0, d_cost=0):
+        """search_batch_device with aggregate_fields_device in the search's place: d_out [npairs][1][height][width]."""
+        self._ck(self.L.gpc_hip_aggregate_batch_device(self.h, C.c_void_p(d_rawL), C.c_void_p(d_rawR), int(width), int(height),
+                                                       int(npairs), C.byref(settings), int(refine_radius), C.byref(fill),
+                                                       C.byref(aggregate), C.byref(prm), C.c_void_p(d_out), C.c_void_p(d_state or 0),
+                                                       C.c_void_p(d_label or 0), C.c_void_p(d_stats or 0), C.c_void_p(d_fwd or 0),
+                                                       C.c_void_p(d_level or 0), C.c_void_p(d_counts or 0), C.c_void_p(d_ncand or 0),
+                                                       C.c_void_p(d_cost or 0)))
+
+    def aggregate_sequence_device(self, d_frames, width, height, nframes, settings, fill, aggregate, prm, d_out, d_state=0, d_label=0,
+                                  d_stats=0, d_fwd=0, d_level=0, refine_radius=0, d_counts=0, d_ncand=0, d_cost=0):
+        """search_sequence_device with aggregate_fields_device in the search's place: d_out [nframes-1][2][height][width]."""
+        self._ck(self.L.gpc_hip_aggregate_sequence_device(self.h, C.c_void_p(d_frames), int(width), int(height), int(nframes),
+                                                          C.byref(settings), int(refine_radius), C.byref(fill), C.byref(aggregate),
+                                                          C.byref(prm), C.c_void_p(d_out), C.c_void_p(d_state or 0),
+                                                          C.c_void_p(d_label or 0), C.c_void_p(d_stats or 0), C.c_void_p(d_fwd or 0),
+                                                          C.c_void_p(d_level or 0), C.c_void_p(d_counts or 0), C.c_void_p(d_ncand or 0),
+                                                          C.c_void_p(d_cost or 0)))
+
+    def aggregate_fields(self, field, imgL, imgR, prm=None, want_cost=True, want_choice=True, want_stats=True, want_agg=True):
+        """A host field [P, C, height, width] int32 and images [P, height, width] uint8 -> (out [P, C, height, width] int32, cost
+        [P, height, width] uint16, choice [P, height, width] uint8, stats [P, 4] int32, agg [P, height, width] uint32; None where
+        not wanted)."""
+        field = np.ascontiguousarray(field, np.int32)
+        imgL, imgR = np.ascontiguousarray(imgL, np.uint8), np.ascontiguousarray(imgR, np.uint8)
+        if field.ndim != 4 or field.shape[0] < 1:
+            raise ValueError("field: [P, C, height, width] int32")
+        P, Cn, H, W = field.shape
+        if imgL.shape != (P, H, W) or imgR.shape != (P, H, W):
+            raise ValueError("imgL, imgR: [P, height, width] uint8")
+        prm = prm if prm is not None else Aggregate()
+        out = np.empty(field.shape, np.int32)
+        cost = np.empty((P, H, W), np.uint16) if want_cost else None
+        choice = np.empty((P, H, W), np.uint8) if want_choice else None
+        stats = np.empty((P, 4), np.int32) if want_stats else None
+        agg = np.empty((P, H, W), np.uint32) if want_agg else None
+        self._ck(self.L.gpc_hip_aggregate_fields(self.h, _ptr(field), _ptr(imgL), _ptr(imgR), Cn, W, H, P, C.byref(prm), _ptr(out),
+                                                 _ptr(cost), _ptr(choice), _ptr(stats), _ptr(agg)))
+        return out, cost, choice, stats, agg
 
     # ---- complete cleaned fields (gpc_hip_inpaint_*): holes take the guided weighted mean of the valued pixels around them
     def inpaint_fields_device(self, d_field, d_guide, channels, width, height, npairs, prm, d_out, d_pass=0, d_stats=0):

@@ -27,11 +27,13 @@
 #include <thread>
 #include <vector>
 
+#include "aggregate_host.h"
 #include "clean_host.h"
 #include "dense_host.h"
 #include "field_score_host.h"
 #include "gpc_device.h"
 #include "inpaint_host.h"
+#include "k_aggregate.h"
 #include "k_clean.h"
 #include "k_consensus.h"
 #include "k_dense.h"
@@ -64,7 +66,7 @@
 
 // Eight sections of the host code below are cut out at their rules into files of their own, csrc/host_*.h, and included where
 // they stood: host_staging.h (what scoring, tracks and the stages after them share), host_consensus.h, host_refine.h,
-// host_pyramid.h, host_dense.h, host_quads.h, host_clean.h, host_inpaint.h and host_field_score.h (host_search.h came between).  They are parts of THIS translation unit, not self-contained headers: each needs what
+// host_pyramid.h, host_dense.h, host_quads.h, host_clean.h, host_inpaint.h and host_field_score.h (host_search.h and host_aggregate.h came between).  They are parts of THIS translation unit, not self-contained headers: each needs what
 // stands above its include, and `#pragma once` is all the guard it has.  Each says its linkage once: an anonymous namespace
 // with its types, helpers and templates, then one extern "C" block with its entry points.  Everything else is still here.
 
@@ -411,6 +413,9 @@ struct gpc_hip_ctx {
   // completing fields (gpc_hip_inpaint_*): the pass plane where the caller passes none; the control words (pixels filled per
   // pass, stats where the caller passes none, holes per tile)
   DevBuf ip_pass, ip_ctl;
+  // aggregating the search's costs (gpc_hip_aggregate_*): the cost volume of a group of pairs, then its path volumes
+  DevBuf ag_ws;
+  int64_t agg_group_bytes = AG_GROUP_BYTES;  // GPC_HIP_AGG_GROUP_BYTES: what the volumes of one group of pairs may take (tests)
   // quads over a stereo sequence (gpc_hip_quads_*): the per-pixel planes of a group of steps followed by its owner words
   // (one fill covers both), the candidate i' per support slot, the quad counts per chunk; the image-major copies of the
   // statistics words, code images and (32-bit codes) candidate bytes of each side, which the two flow joins of
@@ -2302,6 +2307,10 @@ int gpc_hip_create(int device, gpc_hip_ctx** out) {
     const int v = atoi(e);
     if (v >= 1 && v <= 1024) c->quad_steps = v;
   }
+  if (const char* e = getenv("GPC_HIP_AGG_GROUP_BYTES")) {
+    const long long v = atoll(e);
+    if (v >= 1 && v <= AG_GROUP_BYTES) c->agg_group_bytes = v;
+  }
   const char* et = getenv("GPC_HIP_EXPAND_THREADS");
   if (et && atoi(et) > 0 && atoi(et) <= 64) c->expand_threads = atoi(et);
   if (const char* e = getenv("GPC_HIP_UPLOAD")) c->upload_mode = atoi(e);
@@ -4154,6 +4163,7 @@ int gpc_hip_track_stream_read_tracks(gpc_hip_ctx* c, gpc_hip_track_stream* s, in
 #include "host_quads.h"
 #include "host_clean.h"
 #include "host_search.h"
+#include "host_aggregate.h"
 #include "host_inpaint.h"
 #include "host_field_score.h"
 
