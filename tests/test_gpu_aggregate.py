@@ -225,6 +225,31 @@ def test_extremes(ctx, Cn):
         assert got[3][0, 0] > 0 and got[3][0, 2] > 0 and got[3][0, 1] == 0
 
 
+@pytest.mark.parametrize("Cn", [1, 2])
+def test_a_path_starts_anew_behind_a_pixel_that_is_not_live(ctx, Cn):
+    """The directed case of DESIGN.md 4.20's mutation record for `live` (mutant (c), which no test fails because it changes
+    no value): a hole and a pixel whose targets all lie outside the image stand in the middle of a row and of a column of
+    random images; the expectation is aggregate_plain's, pixel by pixel, and behind either pixel every path that comes
+    through it holds the raw cost again -- one direction at a time, so that the sum is the path's own value."""
+    W, H = 11, 7
+    L, R = su.images("random", W, H, 1, Cn, seed=9)
+    field = np.zeros((1, Cn, H, W), np.int32)
+    field[0, 0, 3, 4] = N                                                     # a hole
+    field[0, 0, 3, 7] = 256 * (W + 5) * (1 if Cn == 2 else -1)                # every target right of the image
+    field[0, 0, 1, 5] = N
+    for paths in (1, 2, 4, 8, 15):
+        prm = (1, 1, 1, 0xFFFF, 7, 40, paths)
+        got = aggregate_device(ctx, dev(field), dev(L), dev(R), field.shape, prm)
+        out, cost, choice, state, agg = au.aggregate_plain(field[0], L[0], R[0], prm)
+        same(got, (out[None], cost[None], choice[None], np.bincount(state.ravel(), minlength=4)[None, :4].astype(np.int32), agg[None]),
+             ("not live", Cn, paths))
+        assert state[3, 4] == 1 and state[3, 7] == 2 and got[3][0, 1] == 2 and got[3][0, 2] == 1
+        if paths < 15:                                                        # the pixel behind, in the path's direction: S is the raw cost
+            dx, dy = {1: (1, 0), 2: (-1, 0), 4: (0, 1), 8: (0, -1)}[paths]
+            for x, y in ((4 + dx, 3 + dy), (7 + dx, 3 + dy), (5 + dx, 1 + dy)):
+                assert state[y, x] in (0, 3) and got[4][0, y, x] == got[1][0, y, x], (paths, x, y)
+
+
 def test_more_than_one_workspace_group(monkeypatch):
     """GPC_HIP_AGG_GROUP_BYTES (read when a context is made) shrinks the budget of a group of pairs: 5 pairs in groups of 1, of
     2 and in one go give the same bytes, in place too"""
