@@ -1292,6 +1292,64 @@ int gpc_hip_aggregate_fields(gpc_hip_ctx* ctx, const int32_t* field, const uint8
                              int width, int height, int npairs, const gpc_aggregate* prm, int32_t* out, uint16_t* cost,
                              uint8_t* choice, int32_t* stats, uint32_t* agg);
 
+/* ---- propagate field values between neighbours --------------------------------------------- */
+/* The fill interpolates across object edges, so the prior there is off by many pixels, and the search and the aggregation
+ * above look at most `range` <= 2 whole pixels around it: at an edge no choice among their candidates can be right.  The
+ * right value usually exists a few pixels away, on the correct side of the edge.  This stage is spatial propagation
+ * (PatchMatch; the grid candidates of ELAS): a pixel tries the values of its neighbours as candidates and keeps whichever the
+ * two images agree with best.  Run at strides that halve from `span` down to 1, a value travels up to about twice `span` (it
+ * must be the best at each pixel it passes through).  The stage sits between the fill and the search, which supplies the
+ * sub-pixel part afterwards.  The reference has no counterpart; the rule is made of integers only, so that every
+ * implementation of it gives the same bytes.
+ *
+ * Inputs: as in the search block -- field[P][C][height][width] int32 in 1/256 pixel, C = 1 or 2, imgL and imgR
+ *   [P][height][width] uint8.  The hole test (F_0 is GPC_DENSE_NONE), the rounding r_c = sgn(F_c) * ((|F_c| + 128) >> 8) in 64
+ *   bits, and cost(p, t) with clamped addresses are exactly steps 1 and 2 of the search block.  r = radius, N = iterations.
+ * Iterations: iteration i = 0 .. N-1 has the stride s_i = max(1, span >> i).  It reads ONLY the field that iteration i-1
+ *   wrote (iteration 0 reads the input) and writes a whole new field: a Jacobi step -- no pixel sees a value written in the
+ *   same iteration, so the result does not depend on any order of execution.
+ * Per pixel p = (x, y) of iteration i, s = s_i:
+ *   1 a hole stays a hole, and every channel is copied as it is.
+ *   2 candidate sources, in this fixed order, with index j:  0: p itself   1: (x - s, y)   2: (x + s, y)   3: (x, y - s)
+ *     4: (x, y + s)   and with neighbours = 8:  5: (x - s, y - s)   6: (x + s, y - s)   7: (x - s, y + s)   8: (x + s, y + s).
+ *     A source outside the image gives no candidate (it is not clamped).  A source that is a hole gives no candidate.
+ *   3 candidate j with source q has the whole-pixel displacement r(q): its target is t = (x - r_0(q), y) with C = 1 and
+ *     t = (x + r_0(q), y + r_1(q)) with C = 2.  It is ADMISSIBLE iff t lies inside the image.
+ *   4 the winner is the admissible candidate with the lexicographically smallest (cost(p, t), j): on equal cost the pixel's
+ *     own value wins, then the fixed order.  (A candidate with the same displacement as an earlier one has the same cost and
+ *     can never win; an implementation may skip it.)
+ *   5 the value written: if j = 0 wins, every channel of p unchanged, sub-pixel bits included; if j > 0 wins, 256 * r_c(q) in
+ *     every channel (admissibility bounds |r_c| by the image size, so this cannot overflow); if no candidate is admissible
+ *     the pixel is UNMATCHED and its channels are copied unchanged.  The stage replaces values and never removes one.
+ * Outputs; every element of every output is written:
+ *   out[P][C][height][width]: the field after iteration N-1.  out == field (the same pointer) is allowed and gives the same
+ *     bytes.
+ *   cost[P][height][width] uint16 (optional): the winner's cost in the LAST iteration; 0xFFFF for holes and unmatched pixels.
+ *   choice[P][height][width] uint8 (optional): the winner's j in the last iteration; 255 for holes and unmatched pixels.
+ *   stats[P][N][4] int32 (optional), per iteration: the numbers of pixels that kept their own value, holes, unmatched pixels
+ *     and pixels moved to a neighbour's value.
+ * The refusals and limits of the search block apply; a parameter out of its range gives GPC_E_INVALID.  out may not overlap
+ * the images, and may not overlap field other than being it. */
+typedef struct gpc_propagate {
+  int32_t radius;      /* r, 1 .. 4: the window is (2 r + 1)^2                                  */
+  int32_t span;        /* 1 .. 64: the stride of the first iteration                            */
+  int32_t iterations;  /* N, 1 .. 16                                                            */
+  int32_t neighbours;  /* 4 or 8                                                                */
+} gpc_propagate;       /* documented defaults: 2, 1, 6, 8 -- the point of a small grid with the lowest error over
+                        * all pixels after propagate -> search on four synthetic scenes  */
+/* A field and its two images already on the device.  A pure function of its arguments: no forest is needed, and the call
+ * only queues work on the context's stream (a clear of the stats, with out == field and an odd N one copy of the field, and
+ * N launches whatever the data); read the outputs after gpc_hip_synchronize or another wait on the stream.  Workspace, owned
+ * by the context and grown on demand: one field's bytes (none with N = 1 and out apart from field). */
+int gpc_hip_propagate_fields_device(gpc_hip_ctx* ctx, const int32_t* d_field, const uint8_t* d_imgL, const uint8_t* d_imgR,
+                                    int channels, int width, int height, int npairs, const gpc_propagate* prm, int32_t* d_out,
+                                    uint16_t* d_cost, uint8_t* d_choice, int32_t* d_stats);
+/* A host field, images and outputs through gpc_hip_propagate_fields_device; synchronous, in chunks of at most 16 pairs,
+ * pageable arrays through the context's page-locked arena.  What comes back equals the device form byte for byte. */
+int gpc_hip_propagate_fields(gpc_hip_ctx* ctx, const int32_t* field, const uint8_t* imgL, const uint8_t* imgR, int channels,
+                             int width, int height, int npairs, const gpc_propagate* prm, int32_t* out, uint16_t* cost,
+                             uint8_t* choice, int32_t* stats);
+
 /* ---- complete cleaned dense fields, guided by the image ------------------------------------ */
 /* The cleaner's output is a field with holes: failed checks (occlusions, halos), speckles, and whatever the fill never
  * valued.  This stage closes them by an edge-aware completion: a hole takes the weighted mean of the valued pixels around

@@ -164,6 +164,15 @@ class Aggregate(C.Structure):
         super().__init__(int(radius), int(range), int(subpixel), int(max_cost), int(p1), int(p2), int(paths))
 
 
+class Propagate(C.Structure):
+    """gpc_propagate: the parameters of the propagation of field values between neighbours (gpc_hip_propagate_*); the
+    documented defaults."""
+    _fields_ = [("radius", C.c_int32), ("span", C.c_int32), ("iterations", C.c_int32), ("neighbours", C.c_int32)]
+
+    def __init__(self, radius=2, span=1, iterations=6, neighbours=8):
+        super().__init__(int(radius), int(span), int(iterations), int(neighbours))
+
+
 class Inpaint(C.Structure):
     """gpc_inpaint: the parameters of the guided completion (gpc_hip_inpaint_*); the documented defaults."""
     _fields_ = [("radius", C.c_int32), ("range_shift", C.c_int32), ("min_weight", C.c_int32), ("passes", C.c_int32)]
@@ -236,6 +245,7 @@ SYMBOLS = [
     "gpc_hip_score_fields_device", "gpc_hip_score_fields",
     "gpc_hip_aggregate_fields_device", "gpc_hip_aggregate_batch_device", "gpc_hip_aggregate_sequence_device",
     "gpc_hip_aggregate_fields",
+    "gpc_hip_propagate_fields_device", "gpc_hip_propagate_fields",
 ]
 
 
@@ -433,6 +443,9 @@ def load():
     L.gpc_hip_aggregate_fields_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   C.POINTER(Aggregate), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gpc_hip_aggregate_fields.argtypes = L.gpc_hip_aggregate_fields_device.argtypes
+    L.gpc_hip_propagate_fields_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(Propagate), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_propagate_fields.argtypes = L.gpc_hip_propagate_fields_device.argtypes
     L.gpc_hip_aggregate_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
                                                  C.POINTER(Densify), C.POINTER(Aggregate), C.POINTER(Clean)] + [C.c_void_p] * 9
     L.gpc_hip_aggregate_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
@@ -1437,6 +1450,36 @@ class Context:
         stats = np.empty((P, 4), np.int32) if want_stats else None
         self._ck(self.L.gpc_hip_search_fields(self.h, _ptr(field), _ptr(imgL), _ptr(imgR), Cn, W, H, P, C.byref(prm), _ptr(out),
                                               _ptr(cost), _ptr(choice), _ptr(stats)))
+        return out, cost, choice, stats
+
+    # ---- propagate field values between neighbours (gpc_hip_propagate_*): between the fill and the search
+    def propagate_fields_device(self, d_field, d_imgL, d_imgR, channels, width, height, npairs, prm, d_out, d_cost=0, d_choice=0,
+                                d_stats=0):
+        """A field [npairs][channels][height][width] int32 and the images [npairs][height][width] uint8 already in HBM -> d_out
+        of the field's shape (it may be d_field itself), d_cost [npairs][height][width] uint16 and d_choice
+        [npairs][height][width] uint8 of the last iteration, d_stats [npairs][iterations][4] int32 (all optional);
+        asynchronous, no forest needed.  Pointers are integers."""
+        self._ck(self.L.gpc_hip_propagate_fields_device(self.h, C.c_void_p(d_field), C.c_void_p(d_imgL), C.c_void_p(d_imgR), int(channels),
+                                                        int(width), int(height), int(npairs), C.byref(prm), C.c_void_p(d_out),
+                                                        C.c_void_p(d_cost or 0), C.c_void_p(d_choice or 0), C.c_void_p(d_stats or 0)))
+
+    def propagate_fields(self, field, imgL, imgR, prm=None, want_cost=True, want_choice=True, want_stats=True):
+        """A host field [P, C, height, width] int32 and images [P, height, width] uint8 -> (out [P, C, height, width] int32, cost
+        [P, height, width] uint16, choice [P, height, width] uint8, stats [P, iterations, 4] int32; None where not wanted)."""
+        field = np.ascontiguousarray(field, np.int32)
+        imgL, imgR = np.ascontiguousarray(imgL, np.uint8), np.ascontiguousarray(imgR, np.uint8)
+        if field.ndim != 4 or field.shape[0] < 1:
+            raise ValueError("field: [P, C, height, width] int32")
+        P, Cn, H, W = field.shape
+        if imgL.shape != (P, H, W) or imgR.shape != (P, H, W):
+            raise ValueError("imgL, imgR: [P, height, width] uint8")
+        prm = prm if prm is not None else Propagate()
+        out = np.empty(field.shape, np.int32)
+        cost = np.empty((P, H, W), np.uint16) if want_cost else None
+        choice = np.empty((P, H, W), np.uint8) if want_choice else None
+        stats = np.empty((P, max(1, int(prm.iterations)), 4), np.int32) if want_stats else None
+        self._ck(self.L.gpc_hip_propagate_fields(self.h, _ptr(field), _ptr(imgL), _ptr(imgR), Cn, W, H, P, C.byref(prm), _ptr(out),
+                                                 _ptr(cost), _ptr(choice), _ptr(stats)))
         return out, cost, choice, stats
 
     # ---- aggregate the search's costs along scanlines (gpc_hip_aggregate_*): the search's candidates, chosen with a smoothness term

@@ -46,6 +46,7 @@
 #include "k_inpaint.h"
 #include "k_partition.h"
 #include "k_preprocess.h"
+#include "k_propagate.h"
 #include "k_pyramid.h"
 #include "k_quad.h"
 #include "k_refine.h"
@@ -60,13 +61,14 @@
 #include "k_train_forest.h"
 #include "k_union.h"
 #include "owners.h"
+#include "propagate_host.h"
 #include "pyramid_host.h"
 #include "search_host.h"
 #include "track_stream_host.h"
 
 // Eight sections of the host code below are cut out at their rules into files of their own, csrc/host_*.h, and included where
 // they stood: host_staging.h (what scoring, tracks and the stages after them share), host_consensus.h, host_refine.h,
-// host_pyramid.h, host_dense.h, host_quads.h, host_clean.h, host_inpaint.h and host_field_score.h (host_search.h and host_aggregate.h came between).  They are parts of THIS translation unit, not self-contained headers: each needs what
+// host_pyramid.h, host_dense.h, host_quads.h, host_clean.h, host_inpaint.h and host_field_score.h (host_search.h, host_aggregate.h and host_propagate.h came between).  They are parts of THIS translation unit, not self-contained headers: each needs what
 // stands above its include, and `#pragma once` is all the guard it has.  Each says its linkage once: an anonymous namespace
 // with its types, helpers and templates, then one extern "C" block with its entry points.  Everything else is still here.
 
@@ -416,6 +418,8 @@ struct gpc_hip_ctx {
   // aggregating the search's costs (gpc_hip_aggregate_*): the cost volume of a group of pairs, then its path volumes
   DevBuf ag_ws;
   int64_t agg_group_bytes = AG_GROUP_BYTES;  // GPC_HIP_AGG_GROUP_BYTES: what the volumes of one group of pairs may take (tests)
+  // propagating field values between neighbours (gpc_hip_propagate_*): the other field of the iterations' ping-pong
+  DevBuf pg_ws;
   // quads over a stereo sequence (gpc_hip_quads_*): the per-pixel planes of a group of steps followed by its owner words
   // (one fill covers both), the candidate i' per support slot, the quad counts per chunk; the image-major copies of the
   // statistics words, code images and (32-bit codes) candidate bytes of each side, which the two flow joins of
@@ -4164,6 +4168,7 @@ int gpc_hip_track_stream_read_tracks(gpc_hip_ctx* c, gpc_hip_track_stream* s, in
 #include "host_clean.h"
 #include "host_search.h"
 #include "host_aggregate.h"
+#include "host_propagate.h"
 #include "host_inpaint.h"
 #include "host_field_score.h"
 
