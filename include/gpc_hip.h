@@ -1350,6 +1350,64 @@ int gpc_hip_propagate_fields(gpc_hip_ctx* ctx, const int32_t* field, const uint8
                              int width, int height, int npairs, const gpc_propagate* prm, int32_t* out, uint16_t* cost,
                              uint8_t* choice, int32_t* stats);
 
+/* ---- close holes along scanlines from the background side ----------------------------------- */
+/* The cleaner takes out the occluded band beside a foreground object, and the completion below fills it with a weighted
+ * mean of both sides of the edge: wrong for every pixel of an occlusion, whatever the weights.  This stage is a choice, not
+ * a mean (the gap interpolation of ELAS, the occlusion filling of SGM): along the scanline through a hole, look at the two
+ * valued ends of its run of holes; where they agree, interpolate between them; where they disagree the run is a depth edge,
+ * and the hole takes the background end.  The stage sits between the cleaner and the completion, which then only closes
+ * what is left.  The reference has no counterpart; the rule is made of integers only, so that every implementation of it
+ * gives the same bytes.
+ *
+ * Inputs: P = npairs fields field[P][C][height][width] int32 in 1/256 pixel, C = 1 or 2; optionally guide[P][height][width]
+ *   uint8 (required with select = 1).  A pixel is a HOLE iff F_0 is GPC_DENSE_NONE, whatever F_1 holds; every other pixel
+ *   is VALUED, and any int32 in F_1 is a value.  All arithmetic is done in 64 bits: nothing is undefined for INT32_MAX or
+ *   INT32_MIN + 1.
+ * Runs: the RUN of a hole p along an axis (horizontal, vertical) is the maximal line of consecutive holes through p in the
+ *   INPUT field; its length is n; its ends are the pixels just before its first and just after its last hole.  An end is a
+ *   valued pixel or lies outside the image.  da and db are p's distances to the first (left / upper) end A and to the second
+ *   end B: da + db = n + 1.
+ * An axis is USABLE for p iff n <= max_gap and either both ends are valued (CLOSED) or exactly one is and border = 1
+ *   (HALF-OPEN).
+ * The axis's candidate:
+ *   half-open: the valued end's value.  Kind BORDER.
+ *   closed with |A_c - B_c| <= discon_q8 in every channel: kind CONTINUOUS.  S_c = A_c * db + B_c * da, N = da + db, and
+ *     the value is sgn(S_c) * ((2 |S_c| + N) div (2 N)): the fill's rounding, half away from zero; the nearer end weighs
+ *     more.
+ *   closed otherwise: kind DISCONTINUOUS.  The value is one end's, with all its channels.  m(E) = sum over c of E_c^2 in
+ *     unsigned 64 bits, g(E) = |I(p) - I(E)| in the guide.  select = 0 (background): the end with the smaller (m, distance
+ *     to p), on equality A -- for a disparity of either sign the farther surface, for a flow the slower one (a stated
+ *     heuristic).  select = 1 (guide): the end with the smaller (g, m, distance), on equality A.
+ * Between the axes: p takes the candidate of the usable axis with the shorter run, on equal length the horizontal one.  A
+ *   hole with no usable axis stays a hole.  Valued pixels never change.  No filled value is ever read: every end is a
+ *   pixel valued on input.
+ * Outputs; every element of every output is written:
+ *   out[P][C][height][width]; a hole that is left gets GPC_DENSE_NONE in every channel.  out == field (the same pointer) is
+ *     allowed and gives the same bytes; any other overlap of out with field or with the guide is GPC_E_INVALID.
+ *   how[P][height][width] uint8 (optional): 0 valued on input; 1 / 2 / 3 horizontal continuous / discontinuous / border;
+ *     4 / 5 / 6 the same, vertical; 255 a hole that is left.
+ *   stats[P][4] int32 (optional): pixels filled continuous, filled discontinuous, filled border, holes left.
+ * GPC_E_INVALID: a parameter out of its range, channels not 1 or 2, a null required pointer, select = 1 without a guide,
+ * width, height or npairs below 1.  GPC_E_UNSUPPORTED: the limits of the densify block (32768, 2^30, 65535). */
+typedef struct gpc_gapfill {
+  int32_t max_gap;   /* 1 .. 32767: the longest run an axis may close                          */
+  int32_t discon_q8; /* 0 .. 2^24: ends further apart than this in a channel are a depth edge  */
+  int32_t select;    /* 0 background, 1 guide                                                  */
+  int32_t border;    /* 0 or 1: half-open runs are usable                                      */
+} gpc_gapfill;       /* 16 bytes.  Documented defaults: 64, 128, 0, 1 -- the point of a grid with the lowest error over all
+                      * pixels after gapfill -> complete on four synthetic scenes           */
+/* A field (and a guide) already on the device.  A pure function of its arguments: no forest is needed, and the call only
+ * queues work on the context's stream (a clear of the stats and three launches whatever the data); read the outputs after
+ * gpc_hip_synchronize or another wait on the stream.  Workspace, owned by the context and grown on demand: four planes of
+ * uint16 distances, 8 bytes per pixel and pair.  d_guide may be null with select = 0. */
+int gpc_hip_gapfill_fields_device(gpc_hip_ctx* ctx, const int32_t* d_field, const uint8_t* d_guide, int channels, int width,
+                                  int height, int npairs, const gpc_gapfill* prm, int32_t* d_out, uint8_t* d_how,
+                                  int32_t* d_stats);
+/* A host field, guide and outputs through gpc_hip_gapfill_fields_device; synchronous, in chunks of at most 16 pairs,
+ * pageable arrays through the context's page-locked arena.  What comes back equals the device form byte for byte. */
+int gpc_hip_gapfill_fields(gpc_hip_ctx* ctx, const int32_t* field, const uint8_t* guide, int channels, int width, int height,
+                           int npairs, const gpc_gapfill* prm, int32_t* out, uint8_t* how, int32_t* stats);
+
 /* ---- complete cleaned dense fields, guided by the image ------------------------------------ */
 /* The cleaner's output is a field with holes: failed checks (occlusions, halos), speckles, and whatever the fill never
  * valued.  This stage closes them by an edge-aware completion: a hole takes the weighted mean of the valued pixels around

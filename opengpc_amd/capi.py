@@ -173,6 +173,14 @@ class Propagate(C.Structure):
         super().__init__(int(radius), int(span), int(iterations), int(neighbours))
 
 
+class Gapfill(C.Structure):
+    """gpc_gapfill: the parameters of the scanline hole closing (gpc_hip_gapfill_*); the documented defaults."""
+    _fields_ = [("max_gap", C.c_int32), ("discon_q8", C.c_int32), ("select", C.c_int32), ("border", C.c_int32)]
+
+    def __init__(self, max_gap=64, discon_q8=128, select=0, border=1):
+        super().__init__(int(max_gap), int(discon_q8), int(select), int(border))
+
+
 class Inpaint(C.Structure):
     """gpc_inpaint: the parameters of the guided completion (gpc_hip_inpaint_*); the documented defaults."""
     _fields_ = [("radius", C.c_int32), ("range_shift", C.c_int32), ("min_weight", C.c_int32), ("passes", C.c_int32)]
@@ -246,6 +254,7 @@ SYMBOLS = [
     "gpc_hip_aggregate_fields_device", "gpc_hip_aggregate_batch_device", "gpc_hip_aggregate_sequence_device",
     "gpc_hip_aggregate_fields",
     "gpc_hip_propagate_fields_device", "gpc_hip_propagate_fields",
+    "gpc_hip_gapfill_fields_device", "gpc_hip_gapfill_fields",
 ]
 
 
@@ -446,6 +455,9 @@ def load():
     L.gpc_hip_propagate_fields_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   C.POINTER(Propagate), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gpc_hip_propagate_fields.argtypes = L.gpc_hip_propagate_fields_device.argtypes
+    L.gpc_hip_gapfill_fields_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Gapfill),
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gpc_hip_gapfill_fields.argtypes = L.gpc_hip_gapfill_fields_device.argtypes
     L.gpc_hip_aggregate_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
                                                  C.POINTER(Densify), C.POINTER(Aggregate), C.POINTER(Clean)] + [C.c_void_p] * 9
     L.gpc_hip_aggregate_sequence_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Settings), C.c_int,
@@ -1481,6 +1493,35 @@ class Context:
         self._ck(self.L.gpc_hip_propagate_fields(self.h, _ptr(field), _ptr(imgL), _ptr(imgR), Cn, W, H, P, C.byref(prm), _ptr(out),
                                                  _ptr(cost), _ptr(choice), _ptr(stats)))
         return out, cost, choice, stats
+
+    # ---- close holes along scanlines from the background side (gpc_hip_gapfill_*): between the cleaner and the completion
+    def gapfill_fields_device(self, d_field, d_guide, channels, width, height, npairs, prm, d_out, d_how=0, d_stats=0):
+        """A field [npairs][channels][height][width] int32 and (required with select = 1, else it may be 0) a guide
+        [npairs][height][width] uint8 already in HBM -> d_out of the field's shape (it may be d_field itself), d_how
+        [npairs][height][width] uint8, d_stats [npairs][4] int32 (both optional); asynchronous, no forest needed.  Pointers
+        are integers."""
+        self._ck(self.L.gpc_hip_gapfill_fields_device(self.h, C.c_void_p(d_field), C.c_void_p(d_guide or 0), int(channels), int(width),
+                                                      int(height), int(npairs), C.byref(prm), C.c_void_p(d_out), C.c_void_p(d_how or 0),
+                                                      C.c_void_p(d_stats or 0)))
+
+    def gapfill_fields(self, field, guide=None, prm=None, want_how=True, want_stats=True):
+        """A host field [P, C, height, width] int32 and optionally a guide [P, height, width] uint8 -> (out [P, C, height,
+        width] int32, how [P, height, width] uint8, stats [P, 4] int32; None where not wanted)."""
+        field = np.ascontiguousarray(field, np.int32)
+        if field.ndim != 4 or field.shape[0] < 1:
+            raise ValueError("field: [P, C, height, width] int32")
+        P, Cn, H, W = field.shape
+        if guide is not None:
+            guide = np.ascontiguousarray(guide, np.uint8)
+            if guide.shape != (P, H, W):
+                raise ValueError("guide: [P, height, width] uint8")
+        prm = prm if prm is not None else Gapfill()
+        out = np.empty(field.shape, np.int32)
+        how = np.empty((P, H, W), np.uint8) if want_how else None
+        stats = np.empty((P, 4), np.int32) if want_stats else None
+        self._ck(self.L.gpc_hip_gapfill_fields(self.h, _ptr(field), _ptr(guide), Cn, W, H, P, C.byref(prm), _ptr(out), _ptr(how),
+                                               _ptr(stats)))
+        return out, how, stats
 
     # ---- aggregate the search's costs along scanlines (gpc_hip_aggregate_*): the search's candidates, chosen with a smoothness term
     def aggregate_fields_device(self, d_field, d_imgL, d_imgR, channels, width, height, npairs, prm, d_out, d_cost=0, d_choice=0,

@@ -31,6 +31,7 @@
 #include "clean_host.h"
 #include "dense_host.h"
 #include "field_score_host.h"
+#include "gapfill_host.h"
 #include "gpc_device.h"
 #include "inpaint_host.h"
 #include "k_aggregate.h"
@@ -39,6 +40,7 @@
 #include "k_dense.h"
 #include "k_extract.h"
 #include "k_field_score.h"
+#include "k_gapfill.h"
 #include "k_global.h"
 #include "k_hash.h"
 #include "k_hashtable.h"
@@ -68,7 +70,7 @@
 
 // Eight sections of the host code below are cut out at their rules into files of their own, csrc/host_*.h, and included where
 // they stood: host_staging.h (what scoring, tracks and the stages after them share), host_consensus.h, host_refine.h,
-// host_pyramid.h, host_dense.h, host_quads.h, host_clean.h, host_inpaint.h and host_field_score.h (host_search.h, host_aggregate.h and host_propagate.h came between).  They are parts of THIS translation unit, not self-contained headers: each needs what
+// host_pyramid.h, host_dense.h, host_quads.h, host_clean.h, host_inpaint.h and host_field_score.h (host_search.h, host_aggregate.h, host_propagate.h and host_gapfill.h came between).  They are parts of THIS translation unit, not self-contained headers: each needs what
 // stands above its include, and `#pragma once` is all the guard it has.  Each says its linkage once: an anonymous namespace
 // with its types, helpers and templates, then one extern "C" block with its entry points.  Everything else is still here.
 
@@ -420,6 +422,8 @@ struct gpc_hip_ctx {
   int64_t agg_group_bytes = AG_GROUP_BYTES;  // GPC_HIP_AGG_GROUP_BYTES: what the volumes of one group of pairs may take (tests)
   // propagating field values between neighbours (gpc_hip_propagate_*): the other field of the iterations' ping-pong
   DevBuf pg_ws;
+  // closing holes along scanlines (gpc_hip_gapfill_*): the four planes of distances to the ends of a hole's runs
+  DevBuf gf_ws;
   // quads over a stereo sequence (gpc_hip_quads_*): the per-pixel planes of a group of steps followed by its owner words
   // (one fill covers both), the candidate i' per support slot, the quad counts per chunk; the image-major copies of the
   // statistics words, code images and (32-bit codes) candidate bytes of each side, which the two flow joins of
@@ -4169,6 +4173,7 @@ int gpc_hip_track_stream_read_tracks(gpc_hip_ctx* c, gpc_hip_track_stream* s, in
 #include "host_search.h"
 #include "host_aggregate.h"
 #include "host_propagate.h"
+#include "host_gapfill.h"
 #include "host_inpaint.h"
 #include "host_field_score.h"
 
